@@ -23,7 +23,13 @@ cpu_baseline = the oracle's restatement of the reference C path (gcc -O2, same p
             NetUtil_16BitOnesCplChkSumDataCalc call on a one-buffer NET_BUF) timed on this host's
             cores on a bounded sample of the same workload (rank 0, N=1 only).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]   (torchrun for N>1)
+A plain run sets up, ramps, warms up, times the K steps and prints `value` with the run's configuration.
+`roofline`, `cpu_baseline` and every other figure or check beside the headline (the parity sample
+against the oracle, the read probes, the C5 shard point, the C1 per-datagram figures, the per-rank
+records at N > 1) take runs of their own after the timed region and are made only with --full.
+--dump-outputs DIR writes the checksums of the last timed step to DIR/checksums.npy (float32).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (torchrun for N>1)
 """
 from __future__ import annotations
 
@@ -61,6 +67,14 @@ def parse():
                     help="segments per GPU (default: C2's 1 M at N=1, C5's 16 M shard at N>1)")
     ap.add_argument("--ramp-seconds", type=float, default=0.5,
                     help="untimed clock-ramp phase before the counted warm-up (same launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the event-timed roofline pass, "
+                         "the read probes, roofline.traffic (PMC), the parity sample against the oracle, the C5 "
+                         "shard point, the CPU baseline and the C1 per-datagram figures (a plain run only sets up, "
+                         "warms up, times the K steps and prints the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the checksums of the last timed step to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample, with its indices, of a batch above 1 Mi segments)")
     ap.add_argument("--seg-len", type=int, default=1500)
     ap.add_argument("--pseudo-len", type=int, default=12)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -299,6 +313,26 @@ def host_c2_shard(oracle, start, n, L, plen):
 
 
 C5_SHARD = 1 << 24                  # BASELINE configs[4]: 128 M segments over 8 GPUs = 16 M per GPU
+DUMP_MAX_SEGMENTS = 1 << 20         # --dump-outputs: checksums written over all ranks (4 MB as float32)
+
+
+def dump_outputs(torch, path, out, rank, world):
+    """--dump-outputs: what the step's caller receives, the n checksums of this rank's shard as the
+    last timed step left them in `out`, as float32 (u16 values, exact) in DIR/checksums.npy
+    (DIR/checksums_rank<r>.npy at N > 1). A shard above DUMP_MAX_SEGMENTS / N segments is sampled at
+    fixed indices (seeded by SEED and the rank, sorted), themselves written to <name>_index.npy (float64),
+    so that two builds given the same arguments write arrays that compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    name = "checksums" if world == 1 else f"checksums_rank{rank}"
+    n, cap = out.numel(), max(1, DUMP_MAX_SEGMENTS // world)
+    if n > cap:
+        idx = np.sort(np.random.default_rng([SEED, rank]).choice(n, size=cap, replace=False))
+        vals = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+    else:
+        vals = out.cpu().numpy()
+    np.save(os.path.join(path, name + ".npy"), vals.view(np.uint16).astype(np.float32))
 
 
 def read_probes(torch, netcsum, seg, n16, stream, reps=20):
@@ -611,7 +645,7 @@ def live_traffic(args, n, kernel_desc):
         return None, None, "rocprofv3 not on PATH"
     kfn = kernel_desc.split("::")[-1].split("<")[0] + "<"
     tmp = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--ramp-seconds", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0",
              "--no-cpu-baseline", "--no-c5-point", "--pmc", "off", "--segments", str(n), "--seg-len", str(args.seg_len),
              "--pseudo-len", str(args.pseudo_len)] + [x for kv in args.tune for x in ("--tune", kv)]
     vals = {}
@@ -655,7 +689,7 @@ def live_c5_counters(args):
     if exe is None:
         return {"error": "rocprofv3 not on PATH"}
     tmp = tempfile.mkdtemp(prefix="bench_c5pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--ramp-seconds", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0",
              "--no-cpu-baseline", "--no-c5-point", "--pmc", "off", "--segments", str(C5_SHARD), "--seg-len",
              str(args.seg_len), "--pseudo-len", str(args.pseudo_len)]
     cmd = ["timeout", "-s", "KILL", "180", exe, "--pmc", *C5_COUNTERS, "-d", tmp, "-o", "c5", "--output-format", "csv",
@@ -708,8 +742,42 @@ def load_traffic(path, n_seg, kernel_desc):
     return None, None, why
 
 
+def headline(args, world, n, wall, ramp_launches, backend, ndev):
+    """The result line of a plain run (rank 0): the headline figure from the timed region alone (`wall` =
+    max over ranks of the wall time of the K timed steps) and the run's configuration. --full adds its
+    own measurements to it."""
+    L, plen = args.seg_len, args.pseudo_len
+    value = world * n * (L + plen) * args.steps / wall / 2 ** 30
+    return {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "value_per_gpu": round(value / world, 2),
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ramp_launches": ramp_launches,
+        "ms_per_step": round(wall / args.steps * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u16",
+        "data": "synthetic (device-generated splitmix64 bytes, seed 0x5EED0001, rank shard = slice of one global stream; IPv4 pseudo-headers from the global index)",
+        "config": {"workload": (("C2: 1 M x " if world == 1 and n == 1 << 20 else
+                                 f"C5 shard: {n} x " if n == C5_SHARD else f"{n} x ")
+                                + f"{L} B TCP segments + {plen} B IPv4 pseudo-header per GPU, device-resident, "
+                                "NetUtil_16BitOnesCplChkSumDataCalc per segment"),
+                   "segments_per_gpu": n, "seg_len": L, "pseudo_len": plen,
+                   "global_batch": n * world, "parallelism": f"shard{world} (no collective)",
+                   "dist": "single rank" if world == 1 else f"{world} ranks, backend {backend}, devices: " + (
+                       "one per rank" if backend == "nccl" else f"{ndev} shared (rehearsal)")},
+    }
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps} must be >= 1")
     if world_check(args.gpus) == "launch":
         return launch_ranks(args)
     stage("start")
@@ -792,6 +860,20 @@ def main():
         dist.barrier()
     wall = time.perf_counter() - t0
     stage("timed region done")
+    if args.dump_outputs:                          # `out` is as the last timed step left it
+        dump_outputs(torch, args.dump_outputs, out, rank, world)
+
+    if not args.full:                              # plain run: the headline line only
+        if world > 1:
+            t = torch.tensor([wall], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            wall = float(t.item())
+        if rank == 0:
+            print(json.dumps(headline(args, world, n, wall, ramp_launches, backend, ndev)), flush=True)
+        stage("reported")
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
 
     # roofline pass (untimed for `value`): HIP events on the launch stream around each of K launches
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -858,8 +940,6 @@ def main():
         parity_all = bool(t.item()) if not isinstance(parity_ok, str) else parity_ok
 
     if rank == 0:
-        total_bytes = world * n * (L + plen) * args.steps
-        value = total_bytes / wall / 2 ** 30
         algo_bytes = n * (L + plen + 2)
         traffic, traffic_src = None, None
         traffic_err = "--pmc off" if args.pmc == "off" else None
@@ -870,27 +950,8 @@ def main():
             traffic, traffic_src, traffic_err = load_traffic(args.traffic_json, n, kernel_desc)
             if live_err:
                 traffic_err = f"live PMC failed ({live_err}); " + (traffic_err or "committed summary used")
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "value_per_gpu": round(value / world, 2),
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ramp_launches": ramp_launches,
-            "ms_per_step": round(wall / args.steps * 1e3, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u16",
-            "data": "synthetic (device-generated splitmix64 bytes, seed 0x5EED0001, rank shard = slice of one global stream; IPv4 pseudo-headers from the global index)",
-            "config": {"workload": (("C2: 1 M x " if world == 1 and n == 1 << 20 else
-                                     f"C5 shard: {n} x " if n == C5_SHARD else f"{n} x ")
-                                    + f"{L} B TCP segments + {plen} B IPv4 pseudo-header per GPU, device-resident, "
-                                    "NetUtil_16BitOnesCplChkSumDataCalc per segment"),
-                       "segments_per_gpu": n, "seg_len": L, "pseudo_len": plen,
-                       "global_batch": n * world, "parallelism": f"shard{world} (no collective)"},
+        line = headline(args, world, n, wall, ramp_launches, backend, ndev)
+        line.update({
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4),
                          "traffic": round(traffic) if traffic is not None else None,
@@ -906,18 +967,13 @@ def main():
                          "run_stream_read_probe_GBps": round(run_probe_gbps, 1),
                          "frac_of_run_stream_read_probe": round(achieved / run_probe_gbps, 4)},
             "parity_sample_ok": parity_all,
-        }
+        })
         if c5 is not None:
             if args.pmc == "live" and "error" not in c5:
                 c5["pmc_live"] = live_c5_counters(args)
             line["c5_shard_point"] = c5
         if ranks is not None:
             line["ranks"] = ranks
-        if world == 1:
-            line["config"]["dist"] = "single rank"
-        else:
-            line["config"]["dist"] = f"{world} ranks, backend {backend}, devices: " + (
-                "one per rank" if backend == "nccl" else f"{ndev} shared (rehearsal)")
         if world == 1 and not args.no_cpu_baseline:
             try:
                 import oracle

@@ -1,6 +1,6 @@
 /* In-stack compile check: the declarations of Source/net_util.h the drop-in implements. The
  * prototypes are the reference's (net_util.h:422-450; tests/test_boundary_cpu.py compares them token
- * for token with the reference header when /root/reference is present). */
+ * for token with the reference header's, recorded in tests/golden/reference_boundary.json). */
 #ifndef NET_UTIL_MODULE_PRESENT
 #define NET_UTIL_MODULE_PRESENT
 #include "cpu_core.h"

@@ -112,3 +112,49 @@ def test_single_rank_without_gpu_fails_loudly():
     r = _run(["--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--pmc", "off"])
     assert r.returncode != 0
     assert "refusing to fold" in r.stderr or "GPU" in r.stderr
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    import sys as _sys
+    b = _bench_module()
+    argv = _sys.argv
+    try:
+        _sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        plain = b.parse()
+        _sys.argv = ["bench.py", "--full", "--dump-outputs", "somewhere"]
+        full = b.parse()
+    finally:
+        _sys.argv = argv
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7
+    assert full.full is True and full.dump_outputs == "somewhere"
+    # the headline line: K timed steps took `wall` seconds, so one step took wall / K
+    line = b.headline(plain, 1, 1 << 20, 0.0014, 8, "nccl", 1)
+    assert line["ms_per_step"] == pytest.approx(0.2) and line["steps"] == 7 and line["dtype"] == "u16"
+    assert line["value"] == pytest.approx((1 << 20) * 1512 * 7 / 0.0014 / 2 ** 30, abs=0.01)
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["metric"] == b.METRIC
+    assert "roofline" not in line and "cpu_baseline" not in line
+
+
+def test_dump_outputs_writes_the_checksums_as_float32(tmp_path):
+    """Whole below the cap, a fixed sorted sample (with its indices) above it; u16 values exact in float32;
+    the same arguments give the same arrays."""
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    b = _bench_module()
+    small = torch.arange(-5, 5, dtype=torch.int16)
+    b.dump_outputs(torch, str(tmp_path / "a"), small, 0, 1)
+    got = np.load(tmp_path / "a" / "checksums.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().view(np.uint16).astype(np.float32))
+    assert got[0] == 65531.0 and not (tmp_path / "a" / "checksums_index.npy").exists()
+    n = b.DUMP_MAX_SEGMENTS + 1000
+    big = (torch.arange(n, dtype=torch.int64) * 7919 % 65536).to(torch.int16)
+    for d, rank in (("b", 1), ("c", 1), ("d", 0)):
+        b.dump_outputs(torch, str(tmp_path / d), big, rank, 2)
+    idx = np.load(tmp_path / "b" / "checksums_rank1_index.npy")
+    vals = np.load(tmp_path / "b" / "checksums_rank1.npy")
+    assert idx.dtype == np.float64 and len(idx) == len(vals) == b.DUMP_MAX_SEGMENTS // 2
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(vals, big.numpy().view(np.uint16)[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "checksums_rank1_index.npy"))
+    assert np.array_equal(vals, np.load(tmp_path / "c" / "checksums_rank1.npy"))
+    assert not np.array_equal(idx, np.load(tmp_path / "d" / "checksums_rank0_index.npy"))

@@ -2,8 +2,9 @@
 
 * the checksum and CRC prototypes of include/netcsum_mi355x.h and of the in-stack stand-in
   tests/instack/net_util.h equal the reference's Source/net_util.h:422-450 token for token, and every NET_BUF field the chain
-  walk reads has the reference's type in Source/net_buf.h:394-598 (skipped where the reference tree
-  is absent, e.g. on the GPU box);
+  walk reads has the reference's type in Source/net_buf.h:394-598 (against what
+  tests/golden/reference_boundary.json records of the two reference headers: the SHA-256 of each
+  prototype's token string and the fields' type names);
 * host/net_util_mi355x.c compiles -Wall -Wextra -Werror -pedantic in both modes — standalone and
   -DNETCSUM_IN_STACK against stack headers whose NET_BUF layout differs from the template mirror —
   with and without the NET_ERR_CFG_ARG_CHK_DBG_EN checks (tests/c/Makefile);
@@ -17,6 +18,8 @@
   stand-in headers configured with every NET_*_CFG_CHK_SUM_OFFLOAD_{RX,TX}_EN enabled, and refuses to
   build against a stack whose offload flags are off (the adapters replace the stack's checksum calls).
 """
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -24,7 +27,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/Source"
+GOLDEN = json.load(open(os.path.join(REPO, "tests", "golden", "reference_boundary.json")))
 CDIR = os.path.join(REPO, "tests", "c")
 VARIANTS = ["standalone_asan", "dbg_asan", "instack_asan", "instack_dbg_asan", "burst_asan", "burst_instack_asan", "tsan"]
 FUNCS = ["NetUtil_16BitOnesCplChkSumHdrCalc", "NetUtil_16BitOnesCplChkSumHdrVerify",
@@ -39,28 +42,30 @@ def _prototype(text, name):
     return " ".join(f"{m.group(1)} {name} ( {m.group(2)} )".replace("*", " * ").replace(",", " , ").split())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+def _sha(text):
+    return hashlib.sha256(text.encode()).hexdigest()
+
+
 def test_prototypes_match_reference_token_for_token():
-    ref = open(os.path.join(REF, "net_util.h")).read()
+    ref = GOLDEN["prototype_sha256"]
     ours = open(os.path.join(REPO, "include", "netcsum_mi355x.h")).read()
     stand_in = open(os.path.join(REPO, "tests", "instack", "net_util.h")).read()
     for f in FUNCS:
-        assert _prototype(ours, f) == _prototype(ref, f)
-        assert _prototype(stand_in, f) == _prototype(ref, f)
+        assert _sha(_prototype(ours, f)) == ref[f], _prototype(ours, f)
+        assert _sha(_prototype(stand_in, f)) == ref[f], _prototype(stand_in, f)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_netbuf_fields_have_reference_types():
-    ref = open(os.path.join(REF, "net_buf.h")).read()
     fields = {"NextBufPtr": "NET_BUF *", "ProtocolHdrType": "NET_PROTOCOL_TYPE", "ICMP_MsgIx": "CPU_INT16U",
               "ICMP_HdrLen": "CPU_INT16U", "TransportHdrIx": "CPU_INT16U", "TransportHdrLen": "CPU_INT16U",
               "DataLen": "NET_BUF_SIZE", "TotLen": "NET_BUF_SIZE", "DataPtr": "CPU_INT08U *"}
-    for hdr in (ref, open(os.path.join(REPO, "tests", "instack", "net_buf.h")).read()):
-        for name, typ in fields.items():
-            m = re.search(r"^\s*(\w+)\s*(\*?)\s*" + name + r"\s*;", hdr, flags=re.M)
-            assert m, name
-            assert (m.group(1) + (" *" if m.group(2) else "")) == typ, (name, m.group(0))
-    assert re.search(r"typedef\s+CPU_INT16U\s+NET_BUF_SIZE\s*;", ref)
+    assert GOLDEN["net_buf_field_types"] == fields
+    hdr = open(os.path.join(REPO, "tests", "instack", "net_buf.h")).read()
+    for name, typ in fields.items():
+        m = re.search(r"^\s*(\w+)\s*(\*?)\s*" + name + r"\s*;", hdr, flags=re.M)
+        assert m, name
+        assert (m.group(1) + (" *" if m.group(2) else "")) == typ, (name, m.group(0))
+    assert GOLDEN["net_buf_size_type"] == "CPU_INT16U"
 
 
 @pytest.fixture(scope="module")

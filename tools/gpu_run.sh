@@ -18,24 +18,24 @@ for s in $STEPS; do
       > $O/${T}_gpu_tests.log 2>&1 || { tail -40 $O/${T}_gpu_tests.log; exit 1; }
     tail -2 $O/${T}_gpu_tests.log ;;
   bench)
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err \
+    timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err \
       || { cat $O/${T}_bench.err; exit 1; }
     cat $O/${T}_bench.json ;;
   bench400)
-    timeout -k 10 300 python bench.py > $O/${T}_bench400.json 2> $O/${T}_bench400.err || { cat $O/${T}_bench400.err; exit 1; }
+    timeout -k 10 300 python bench.py --full > $O/${T}_bench400.json 2> $O/${T}_bench400.err || { cat $O/${T}_bench400.err; exit 1; }
     cat $O/${T}_bench400.json ;;
   c5)
-    timeout -k 10 300 python bench.py --segments 16777216 --steps 50 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --segments 16777216 --steps 50 --warmup 5 --no-cpu-baseline \
       > $O/${T}_c5_bench.json 2> $O/${T}_c5_bench.err || { cat $O/${T}_c5_bench.err; exit 1; }
     cat $O/${T}_c5_bench.json ;;
   prof)
     ( cd /tmp && export TMPDIR=/tmp &&
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${T}_trace -o trace --output-format csv \
-        -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-c5-point --pmc off > $O/${T}_prof_bench.json 2> $O/${T}_prof_trace.err &&
+        -- python3 $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-c5-point --pmc off > $O/${T}_prof_bench.json 2> $O/${T}_prof_trace.err &&
       timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/${T}_fetch -o fetch --output-format csv \
-        -- python3 $R/bench.py --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off > /dev/null 2> $O/${T}_pmc_fetch.err &&
+        -- python3 $R/bench.py --full --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off > /dev/null 2> $O/${T}_pmc_fetch.err &&
       timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $O/${T}_write -o write --output-format csv \
-        -- python3 $R/bench.py --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off > /dev/null 2> $O/${T}_pmc_write.err
+        -- python3 $R/bench.py --full --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off > /dev/null 2> $O/${T}_pmc_write.err
     ) || { tail -20 $O/${T}_prof_trace.err $O/${T}_pmc_*.err; exit 1; }
     cat $O/${T}_prof_bench.json
     d() { dirname "$(find $O/${T}_$1 -name "$1_$2" -print -quit)"; }
@@ -47,11 +47,11 @@ for s in $STEPS; do
             # uses for roofline.traffic at N > 1
     ( cd /tmp && export TMPDIR=/tmp && A="--segments 16777216 --no-cpu-baseline --pmc off" &&
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/${T}c5_trace -o trace --output-format csv \
-        -- python3 $R/bench.py --steps 30 --warmup 5 $A > $O/${T}c5_prof_bench.json 2> $O/${T}c5_prof_trace.err &&
+        -- python3 $R/bench.py --full --steps 30 --warmup 5 $A > $O/${T}c5_prof_bench.json 2> $O/${T}c5_prof_trace.err &&
       timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE -d $O/${T}c5_fetch -o fetch --output-format csv \
-        -- python3 $R/bench.py --steps 3 --warmup 1 --ramp-seconds 0 $A > /dev/null 2> $O/${T}c5_pmc_fetch.err &&
+        -- python3 $R/bench.py --full --steps 3 --warmup 1 --ramp-seconds 0 $A > /dev/null 2> $O/${T}c5_pmc_fetch.err &&
       timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -d $O/${T}c5_write -o write --output-format csv \
-        -- python3 $R/bench.py --steps 3 --warmup 1 --ramp-seconds 0 $A > /dev/null 2> $O/${T}c5_pmc_write.err
+        -- python3 $R/bench.py --full --steps 3 --warmup 1 --ramp-seconds 0 $A > /dev/null 2> $O/${T}c5_pmc_write.err
     ) || { tail -20 $O/${T}c5_prof_trace.err $O/${T}c5_pmc_*.err; exit 1; }
     d() { dirname "$(find $O/${T}c5_$1 -name "$1_$2" -print -quit)"; }
     python tools/pmc_summary.py ${T}c5 "$(d trace kernel_trace.csv)" "$(d fetch counter_collection.csv)" \

@@ -13,7 +13,7 @@ tail -1 "$O/tests.log"
 i=0
 for v in "" "--pseudo-len 0" "--tune xcd=0" "--tune touch=0" "--tune waves=4" "--tune waves=6" "--tune tile=32" ""; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py --segments 16777216 --steps 30 --warmup 5 --no-cpu-baseline --pmc off \
+  timeout -k 10 300 python bench.py --full --segments 16777216 --steps 30 --warmup 5 --no-cpu-baseline --pmc off \
       --no-c5-point $v > "$O/c5_$i.json" 2> "$O/c5_$i.err" || { tail -5 "$O/c5_$i.err"; exit 1; }
   python3 -c "
 import json,sys; d=json.load(open('$O/c5_$i.json')); r=d['roofline']

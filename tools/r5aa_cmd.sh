@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 T=${1:-r5aa}
 O=gpurun_out; mkdir -p $O
 bash tools/gpu_run.sh $T tests smoke bench prof profc5 configs || exit 1
-NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --segments 65536 --steps 50 \
+NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 2 --segments 65536 --steps 50 \
     --warmup 10 > $O/${T}_dist2.json 2> $O/${T}_dist2.err || { tail -20 $O/${T}_dist2.err; exit 1; }
 bash tools/gpu_pmc_all.sh $T c4 pool1520 pool1520mix pool2k pool2kmix || exit 1
 timeout -k 10 300 python -u tools/varlen_pool_probe.py > $O/${T}_varlen_pool_probe.jsonl 2> $O/${T}_varlen_pool_probe.err || { tail $O/${T}_varlen_pool_probe.err; exit 1; }

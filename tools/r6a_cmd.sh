@@ -18,7 +18,7 @@ for sz in 1048576 16777216; do
     eval "CN=\$$p"
     D=$O/${T}_pmc_${sz}_$p
     ( cd /tmp && timeout -s KILL 120 rocprofv3 --pmc $CN -d $D -o p --output-format csv \
-        -- python3 $R/bench.py --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off \
+        -- python3 $R/bench.py --full --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline --no-c5-point --pmc off \
            --segments $sz > $D.json 2> $D.err ) || { tail -5 $D.err; exit 1; }
     ARGS="$ARGS n${sz}_$p=$D"
   done

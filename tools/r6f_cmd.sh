@@ -13,7 +13,7 @@ tail -2 $O/${T}_tests.log
 C5P_VARIANTS=kernel,gather0,nopseudo,run_probe timeout -k 10 300 python -u tools/c5_probe.py > $O/${T}_c5_probe.jsonl 2> $O/${T}_c5_probe.err \
   || { tail $O/${T}_c5_probe.err; exit 1; }
 cat $O/${T}_c5_probe.jsonl
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail $O/${T}_bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err || { tail $O/${T}_bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/${T}_bench.json'))
 print(d['value'], d['roofline']['frac'], d['roofline']['kernel_ms'], d['roofline']['frac_of_run_stream_read_probe'])

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 T=${1:-r6h}
 O=gpurun_out; mkdir -p $O
 bash tools/gpu_run.sh $T tests smoke bench prof profc5 configs || exit 1
-NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --segments 65536 --steps 50 \
+NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 2 --segments 65536 --steps 50 \
     --warmup 10 > $O/${T}_dist2.json 2> $O/${T}_dist2.err || { tail -20 $O/${T}_dist2.err; exit 1; }
 tail -1 $O/${T}_dist2.json | cut -c1-300
 C5P_VARIANTS=kernel,run_probe,run_probe_sleep,nopseudo,d6,w4,w6,s8,s24,xcd0,touch0 timeout -k 10 400 python -u tools/c5_probe.py \

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 T=${1:-r6z}
 O=gpurun_out; mkdir -p $O
 bash tools/gpu_run.sh $T tests smoke bench prof profc5 configs || exit 1
-NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --segments 65536 --steps 50 \
+NETCSUM_BENCH_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --full --gpus 2 --segments 65536 --steps 50 \
     --warmup 10 > $O/${T}_dist2.json 2> $O/${T}_dist2.err || { tail -20 $O/${T}_dist2.err; exit 1; }
 tail -1 $O/${T}_dist2.json | cut -c1-300
 timeout -k 10 300 tools/build/live_read_probe frag2k 2048 42 1480 > $O/${T}_live_read_probe.jsonl 2> $O/${T}_live_read_probe.err \
