@@ -149,6 +149,24 @@ def test_batch_argument_validation_before_device_work():
     assert L.NetUtil_MI355X_TxFinalizeIPv4(16, None, None, big, 1500, 4, None, 1, None) in (219, 218)
 
 
+def test_tune_accept_set_is_the_recorded_one():
+    """NetUtil_MI355X_Tune needs no device: for keys -1..40 and the values of tools/launch_matrix.py
+    (every small value, the powers of two and the 2^20 / 10^6 limits with their neighbours) the NET_ERR
+    is the one recorded in tests/golden/tune_accept.json. Replayed in a thread of its own (knobs are per
+    thread), so this thread's tuning stays at its defaults."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(netcsum.REPO, "tools"))
+    import launch_matrix
+    with open(launch_matrix.GOLDEN_TUNE) as f:
+        want = json.load(f)
+    assert want["values"] == launch_matrix.TUNE_VALUES
+    got = launch_matrix.tune_accept()
+    assert sorted(got) == sorted(want["err"])
+    for key in got:
+        assert got[key] == want["err"][key], f"key {key}"
+
+
 @pytest.mark.skipif(gpu_available(), reason="checks the no-GPU behaviour")
 def test_no_gpu_fails_loudly_without_fallback():
     hb = netcsum.HostBytes(bytes.fromhex("450000730000400040110000c0a80001c0a800c7"))
