@@ -308,7 +308,8 @@ NET_ERR  NetUtil_MI355X_TxFinalizeIP       (void            *d_base,
  *   ICMPv4 type/code/length, net_icmpv4.c:1500-1659) the reference counts that check instead.
  *   IPv4 fragments: the transport checksum covers the reassembled datagram (net_ipv4.c:6523), which
  *   a per-frame burst does not hold; they are verified at the IP header only (DELIVER_L4_UNVERIFIED,
- *   what any offloading NIC does; ChkSumBatchChains verifies reassembled datagrams).
+ *   what any offloading NIC does). RxBurstSums ((2b''') below) also reports each fragment's payload
+ *   sum, from which the host verifies the reassembled datagram where the stack completes it.
  *   IGMP (net_igmp.c:1332) and ICMPv6 types 1/3/4 (net_icmpv6.c:2913) have no offload flag; the
  *   adapter drops their checksum failures too (same decision, same counter), so the stack's own
  *   per-packet call only ever sees valid ones.
@@ -378,6 +379,76 @@ NET_ERR  NetUtil_MI355X_RxBurstTally       (const uint8_t   *h_action,
                                             uint32_t        *ctr);
 
 /* ============================================================================================
+ * (2b''') Fragment payload sums: reassembled datagrams verified under the Rx offload flags.
+ *
+ * A fragment is delivered L4_UNVERIFIED above, the stack reassembles the datagram inside itself and
+ * across bursts (NetIPv4_RxPktFragReasm, net_ipv4.c:6523; the IPv6 reassembly likewise), and with the
+ * Rx offload flags on the transport layers then assume its checksum valid (net_tcp.c:7847-7848,
+ * net_udp.c:1925-1927, net_icmpv4.c:1673-1674). RxBurstSums closes that hole the way NICs do
+ * (Linux's CHECKSUM_COMPLETE): it is RxBurst — d_action / d_flags are byte for byte what RxBurst
+ * writes, fragments stay DELIVER_L4_UNVERIFIED — and also reports per frame the one's-complement sum
+ * of a fragment's IP payload. One's-complement sums add, so the reassembled datagram is verified on
+ * the host from its fragments' records with a few integer adds each (FragSumVerify), without reading
+ * a byte again.
+ *
+ * d_sums[i] for a frame flagged NETCSUM_PKT_FRAGMENT and not MALFORMED:
+ *   len  the fragment's IP payload octets: IPv4 total length - IHL*4; IPv6 the octets after the
+ *        Fragment header, up to 40 + payload length;
+ *   sum  (uint16_t)~NetUtil_16BitOnesCplChkSumDataCalc(buf, NULL, 0, &err) of one NET_BUF holding
+ *        exactly those octets: the reference's folded sum before the complement, as a host-order
+ *        value; 0 only when every octet is 0 (the kernels keep exact integer sums).
+ * Every other frame, and a fragment with an empty payload, gets {0, 0}. IPv4 fragments that fail the
+ * header checksum get their sum all the same (their action drops them). IPv6 fragments behind
+ * Hop-by-Hop / Destination Options / Routing headers, or past the kernels' header window, are summed
+ * by the extension-header walk. d_sums must be 4-byte aligned (one record is one store), n_pkt at
+ * most 2^30 - 1; the other arguments and their checks are RxBurst's.
+ *
+ * RxBurstSumsHost is RxBurstHost with h_sums; it always takes the copy pipeline (4 B more per frame
+ * D2H): the resident burst server does not produce this output.
+ *
+ * FragSumCalc / FragSumVerify (host logic, no device work): frag[0 .. n_frag) are the records of one
+ * datagram's fragments in reassembly order. The result equals DataCalc / DataVerify over a chain of
+ * n_frag NET_BUFs holding the fragments' payloads with that pseudo-header (ppseudo_hdr NULL with
+ * size 0: none), for any lengths: a piece after an odd number of octets enters byte-swapped, as the
+ * octet the reference carries into the next buffer implies (net_util.c:1385-1393), and n_frag == 0
+ * is the reference's NULL chain (an odd pseudo-header's last octet is not summed, net_util.c:1591-
+ * 1611). The reference validates fragments with More Fragments set to multiples of 8 octets
+ * (net_ipv4.c:5320-5334), so in practice the sums simply add. More than 65 535 octets in total
+ * (no IP datagram is longer) returns NET_UTIL_ERR_MI355X_INVALID_ARG; below that bound the reference's
+ * own u32 accumulator cannot wrap (at most 32 768 + 20 half-words of at most 0xFFFF), so folded
+ * 16-bit sums lose nothing against it. NULL frag (with n_frag != 0), NULL result pointer, or a NULL
+ * pseudo-header with a non-zero size return NET_ERR_FAULT_NULL_PTR.
+ * ============================================================================================ */
+typedef struct netcsum_frag_sum {
+    uint16_t sum;   /* host-order value, see above */
+    uint16_t len;   /* payload octets summed; 0 = no sum produced for this frame */
+} NETCSUM_FRAG_SUM;
+
+NET_ERR  NetUtil_MI355X_RxBurstSums        (const void      *d_base,
+                                            const uint64_t  *d_off,
+                                            const uint16_t  *d_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       pkt_len,
+                                            uint32_t         n_pkt,
+                                            uint32_t         rx_cfg,
+                                            uint8_t         *d_action,
+                                            uint8_t         *d_flags,
+                                            NETCSUM_FRAG_SUM *d_sums,
+                                            void            *hip_stream);
+
+NET_ERR  NetUtil_MI355X_FragSumCalc        (const NETCSUM_FRAG_SUM *frag,
+                                            uint32_t         n_frag,
+                                            const void      *ppseudo_hdr,
+                                            CPU_INT16U       pseudo_hdr_size,
+                                            NET_CHK_SUM     *p_chk_sum);
+
+NET_ERR  NetUtil_MI355X_FragSumVerify      (const NETCSUM_FRAG_SUM *frag,
+                                            uint32_t         n_frag,
+                                            const void      *ppseudo_hdr,
+                                            CPU_INT16U       pseudo_hdr_size,
+                                            CPU_BOOLEAN     *p_ok);
+
+/* ============================================================================================
  * (2e) Host-memory forms (the path starts in NIC Rx buffers, IF/net_if.c:6593,
  * and socket Tx buffers, Source/net_sock.c:5531). Same arguments and results as the device forms
  * above with every pointer in HOST memory. The call splits the batch into n_chunks chunks and
@@ -439,6 +510,19 @@ NET_ERR  NetUtil_MI355X_RxBurstHost        (const void      *h_base,
                                             uint32_t         rx_cfg,
                                             uint8_t         *h_action,
                                             uint8_t         *h_flags,
+                                            uint32_t         n_chunks);
+
+/* RxBurstHost with the fragment payload sums of (2b'''); always the copy pipeline. */
+NET_ERR  NetUtil_MI355X_RxBurstSumsHost    (const void      *h_base,
+                                            const uint64_t  *h_off,
+                                            const uint16_t  *h_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       pkt_len,
+                                            uint32_t         n_pkt,
+                                            uint32_t         rx_cfg,
+                                            uint8_t         *h_action,
+                                            uint8_t         *h_flags,
+                                            NETCSUM_FRAG_SUM *h_sums,
                                             uint32_t         n_chunks);
 
 NET_ERR  NetUtil_MI355X_TxBurstHost        (void            *h_base,

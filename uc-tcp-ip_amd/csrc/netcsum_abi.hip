@@ -580,6 +580,7 @@ NET_ERR nchost::pkt_batch(const Tune& t, const PktJob& j) {
     if (j.base == nullptr || (j.off != nullptr) != (j.len != nullptr) || (!j.tx && j.flags == nullptr && j.action == nullptr)) {
         return NET_ERR_FAULT_NULL_PTR;
     }
+    if (j.sums != nullptr && (j.tx || j.ip_ver != 0)) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;   // (Rx, mixed)
     int dev = 0;
     NC_HIP(hipGetDevice(&dev));
     PktPlan p;
@@ -623,8 +624,9 @@ NET_ERR nchost::pkt_batch(const Tune& t, const PktJob& j) {
     }
     if (j.rec_only != nullptr) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;   // (callers check the domain)
     char desc[120];
-    snprintf(desc, sizeof desc, "pkt_batch_kernel<G=%d,K=%d%s,%s,v%d> block=256 tile=%u%s", p.c.group_lanes,
-             p.c.chunks_per_pass, p.c.nt ? ",nt" : "", j.tx ? "tx" : "rx", j.ip_ver, a.tile, p.walk ? " +pkt_v6_walk_kernel" : "");
+    snprintf(desc, sizeof desc, "pkt_batch_kernel<G=%d,K=%d%s,%s,v%d%s> block=256 tile=%u%s", p.c.group_lanes,
+             p.c.chunks_per_pass, p.c.nt ? ",nt" : "", j.tx ? "tx" : "rx", j.ip_ver, !j.tx && a.sums_out ? ",sums" : "", a.tile,
+             p.walk ? " +pkt_v6_walk_kernel" : "");
     netcsum::set_last_launch(desc);
     ScratchLease scratch;                                 // [deferral word, 256 B | flags (own_flags)]
     if (p.walk) {
@@ -805,6 +807,23 @@ NET_ERR NetUtil_MI355X_RxBurst(const void* d_base, const uint64_t* d_off, const 
     PktJob j = pkt_job(d_base, d_off, d_len, stride, pkt_len, n_pkt, d_flags, hip_stream);
     j.action = d_action;
     j.rx_cfg = rx_cfg;
+    return pkt_batch(tls_tune, j);
+}
+
+// RxBurst with the per-frame fragment payload sums (the SUMS instantiations of the same kernels, in the
+// launch RxBurst would have chosen): RxBurst's checks first, then d_sums.
+NET_ERR NetUtil_MI355X_RxBurstSums(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                                   CPU_INT16U pkt_len, uint32_t n_pkt, uint32_t rx_cfg, uint8_t* d_action, uint8_t* d_flags,
+                                   NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
+    if (n_pkt != 0 && d_action == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_pkt != 0 && d_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    // one record is one 4-B store (offsets of the lane-group form's buffer stores: 32 bits)
+    if (((uintptr_t)d_sums & 3u) != 0u || n_pkt > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    PktJob j = pkt_job(d_base, d_off, d_len, stride, pkt_len, n_pkt, d_flags, hip_stream);
+    j.action = d_action;
+    j.rx_cfg = rx_cfg;
+    j.sums = d_sums;
     return pkt_batch(tls_tune, j);
 }
 

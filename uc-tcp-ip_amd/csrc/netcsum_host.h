@@ -87,6 +87,7 @@ struct PktJob {
     hipStream_t           stream = nullptr;
     uint8_t*              action = nullptr;    // Rx: the burst actions (optional), under rx_cfg
     uint32_t              rx_cfg = 0u;
+    NETCSUM_FRAG_SUM*     sums = nullptr;      // Rx, mixed (RxBurstSums): per-frame fragment payload sums
     uint32_t*             fieldpos = nullptr;  // Tx: which fields each packet had written (the host-memory
                                                // forms' records, optional)
     netcsum::PktTxRecord* rec_only = nullptr;  // zero-copy Tx burst: the records alone, no scatter pass

@@ -861,6 +861,7 @@ static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks) 
     const uint32_t n_pkt = h.n;
     uint8_t* h_flags = h.flags;
     uint8_t* h_action = h.action;
+    NETCSUM_FRAG_SUM* h_sums = h.sums;                       // (RxBurstSumsHost: 4 B more per frame D2H)
     const bool tx = h.tx;
     HostCtx* cp = nullptr;
     NET_ERR e = host_ctx(&cp);
@@ -876,13 +877,14 @@ static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks) 
     const uint64_t maxb = plan_chunks(h_off, h_len, stride, h.pkt_len, n_pkt, n_chunks, ch);
     const bool varlen = h_off != nullptr;
     const uint32_t per = ch[0].ns;
-    // device slot: [bytes | offsets | lengths | flags | actions | field positions | records];
+    // device slot: [bytes | offsets | lengths | flags | actions | field positions | records | fragment sums];
     // host slot: [offsets | lengths | records]
     const size_t o_off = al256(maxb), o_len = o_off + al256(varlen ? (size_t)per * 8u : 0u);
     const size_t o_fl = o_len + al256(varlen ? (size_t)per * 2u : 0u), o_act = o_fl + al256(per);
     const size_t o_fp = o_act + al256(per), o_rec = o_fp + al256(tx ? (size_t)per * 4u : 0u);
     const size_t h_rec = varlen ? al256((size_t)per * 8u) + al256((size_t)per * 2u) : 0u;
-    e = ensure_pipe(c, o_rec + al256(tx ? (size_t)per * 8u : 0u), h_rec + (tx ? (size_t)per * 8u : 0u));
+    const size_t o_sum = o_rec + al256(tx ? (size_t)per * 8u : 0u);
+    e = ensure_pipe(c, o_sum + al256(h_sums ? (size_t)per * sizeof(NETCSUM_FRAG_SUM) : 0u), h_rec + (tx ? (size_t)per * 8u : 0u));
     if (e != NET_UTIL_ERR_NONE) return e;
     PipeDrainOnExit guard{c};
     uint8_t* hb = static_cast<uint8_t*>(const_cast<void*>(h.base));
@@ -925,11 +927,15 @@ static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks) 
         job.flags = h_flags ? d + o_fl : nullptr;
         job.action = h_action ? d + o_act : nullptr;
         job.fieldpos = d_fp;
+        job.sums = h_sums ? reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum) : nullptr;
         job.stream = st;
         e = pkt_batch(t, job);
         if (e != NET_UTIL_ERR_NONE) return e;
         if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
         if (h_action) NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, st));
+        if (h_sums) {
+            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, st));
+        }
         if (tx) {
             netcsum::PktBatchArgs g{};
             g.base = d;
@@ -958,7 +964,8 @@ static NET_ERR pkt_host(const PktJob& h, uint32_t n_chunks) {
         return NET_ERR_FAULT_NULL_PTR;
     }
     const Tune& t = tune();
-    if (n_chunks == 0 && t.burst_zc != 0) {   // a burst from a pinned ring: in place
+    // (a burst with fragment sums always takes the copy pipeline: the resident server has no such output)
+    if (n_chunks == 0 && t.burst_zc != 0 && h.sums == nullptr) {   // a burst from a pinned ring: in place
         HostCtx* cp = nullptr;
         NET_ERR e = host_ctx(&cp);
         if (e != NET_UTIL_ERR_NONE) return e;
@@ -992,6 +999,20 @@ NET_ERR NetUtil_MI355X_RxBurstHost(const void* h_base, const uint64_t* h_off, co
     PktJob h = pkt_job(h_base, h_off, h_len, stride, pkt_len, n_pkt, h_flags, nullptr);
     h.action = h_action;
     h.rx_cfg = rx_cfg;
+    return pkt_host(h, n_chunks);
+}
+
+NET_ERR NetUtil_MI355X_RxBurstSumsHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                       CPU_INT16U pkt_len, uint32_t n_pkt, uint32_t rx_cfg, uint8_t* h_action,
+                                       uint8_t* h_flags, NETCSUM_FRAG_SUM* h_sums, uint32_t n_chunks) {
+    if (n_pkt != 0 && h_action == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_pkt != 0 && h_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    if (n_pkt > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    PktJob h = pkt_job(h_base, h_off, h_len, stride, pkt_len, n_pkt, h_flags, nullptr);
+    h.action = h_action;
+    h.rx_cfg = rx_cfg;
+    h.sums = h_sums;
     return pkt_host(h, n_chunks);
 }
 

@@ -79,8 +79,13 @@ struct PktBatchArgs {
     uint32_t*       defer_word;    // IPv6 / mixed: set to defer_tag by a batch kernel that leaves a
     uint32_t        defer_tag;     // datagram EXT_HDR; the walk pass runs only when it holds the tag
     uint32_t        xcd;           // run-stream form: XCD-aware block order (set by the launcher)
+    union {                        // (one slot: the kernels' argument block keeps its size)
     uint32_t*       fieldpos_out;  // Tx (optional): per packet, which checksum fields were written —
                                    // kFieldIP | kFieldL4 | transport field offset (host-memory forms)
+    uint32_t*       sums_out;      // Rx, mixed batches (RxBurstSums; the SUMS instantiations): per packet
+                                   // one NETCSUM_FRAG_SUM as a little-endian dword, sum | len << 16 — a
+                                   // fragment's payload sum and length, 0 for every other packet
+    };
     uint32_t        plan;          // run-stream strided form, the next batch's plan (pkt_plan_block):
                                    // bits 0-7 the whole-span run (0: form 0 not allowed, gaps > 64 B),
                                    // bits 8-15 the longest live-piece run allowed (the bitmap's reach,
@@ -95,6 +100,9 @@ struct PktBatchArgs {
                                    // leaves vl_ctr[0..1] zero; nullptr: done inline
     uint32_t        vl_wide;       // launcher: the deferred pass's grid, wide (1) or 8 blocks (0)
 };
+// sums_out while a datagram waits for the walk pass (lane-group form: an IPv6 fragment whose Fragment
+// header lies past the group's window): no record has len 0 and sum != 0
+constexpr uint32_t kFragSumWalk = 1u;
 constexpr uint32_t kFieldIP = 1u << 31;    // fieldpos_out: the IPv4 header checksum field (+10) written
 constexpr uint32_t kFieldL4 = 1u << 30;    // fieldpos_out: the transport field at (bits 0-15) written
 // One 8-B record per packet of a host-memory Tx batch (pkt_field_gather_kernel): the written field

@@ -123,6 +123,10 @@ struct PktInfo {
     uint32_t pseudo_le;    // little-endian word sum of the pseudo-header (0: none)
     uint32_t proto;
     bool     check_l4;
+    // SUMS instantiations (RxBurstSums) only, IPv6 fragments: the payload octets after the Fragment
+    // header (hlen is then the payload's offset), or the walk pass sums it (header past the window)
+    uint32_t frag_len;
+    bool     frag_walk;
 };
 
 __device__ __forceinline__ uint32_t swap16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
@@ -157,7 +161,7 @@ __device__ __forceinline__ bool ipv6_ext_hdr(uint32_t nh) {
            nh == 135u || nh == 139u || nh == 140u || nh == 253u || nh == 254u;
 }
 
-template <int G, bool TX>
+template <int G, bool TX, bool SUMS = false>
 __device__ __forceinline__ PktInfo pkt_parse_v6(u32x4 v0, uint32_t lead, uint32_t avail, int gbase, uint32_t udp_mode,
                                                 uint32_t d0, uint32_t d1) {   // packet dwords 0 and 1
     PktInfo p{};
@@ -200,6 +204,16 @@ __device__ __forceinline__ PktInfo pkt_parse_v6(u32x4 v0, uint32_t lead, uint32_
     }
     if (p.proto == 44u) {
         p.flags |= F_FRAGMENT;
+        if constexpr (SUMS) {
+            if (off + 8u < tot) {                                // octets after the 8-B Fragment header
+                if (lead + off + 8u <= kWin) {
+                    p.hlen = off + 8u;
+                    p.frag_len = tot - (off + 8u);
+                } else {
+                    p.frag_walk = true;
+                }
+            }
+        }
         return p;
     }
     if (ipv6_ext_hdr(p.proto) || (off != 40u && lead + off + 24u > kWin)) {
@@ -379,11 +393,12 @@ struct PktStore {
 // BS (strided batches): every store is a raw buffer store executed by ALL lanes, the lanes that store
 // nothing carrying an out-of-range offset, so every path issues the same VMEM stores and the
 // compiler's vmcnt bookkeeping stays exact (stores under a lane-0 branch make it conservative).
-template <int G, bool TX, bool BS>
+// SUMS (Rx, RxBurstSums): ps.vals is the packet's NETCSUM_FRAG_SUM record, stored as one dword.
+template <int G, bool TX, bool BS, bool SUMS = false>
 __device__ __forceinline__ void pkt_store(const PktStore& ps, const PktBatchArgs& A) {
     const uint32_t f = (ps.meta >> 16) & 0xFFu;
     const bool me = (ps.meta >> 26) & 1u;
-    if (me && (f & F_EXT_HDR) && A.defer_word != nullptr) {
+    if (me && ((f & F_EXT_HDR) || (SUMS && ps.vals == kFragSumWalk)) && A.defer_word != nullptr) {
         *A.defer_word = A.defer_tag;                             // the walk pass has work (benign race)
     }
     const bool si = TX && ((ps.meta >> 24) & 1u), sl = TX && ((ps.meta >> 25) & 1u);
@@ -414,6 +429,10 @@ __device__ __forceinline__ void pkt_store(const PktStore& ps, const PktBatchArgs
             const __amdgpu_buffer_rsrc_t ra = byte_rsrc(A.action_out, A.action_out ? A.n : 0u);
             store_byte(ra, l4off, me ? ps.idx : kOOB);
         }
+        if constexpr (SUMS) {                                    // (n < 2^30, RxBurstSums checks: 4 n fits the V#)
+            const __amdgpu_buffer_rsrc_t rs = byte_rsrc(A.sums_out, A.n < (1u << 30) ? A.n * 4u : 0u);
+            __builtin_amdgcn_raw_buffer_store_b32(ps.vals, rs, (int)(me && ps.idx < (1u << 30) ? ps.idx * 4u : kOOB), 0, 0);
+        }
     } else {
         if (!me) {
             return;
@@ -433,10 +452,13 @@ __device__ __forceinline__ void pkt_store(const PktStore& ps, const PktBatchArgs
         if (TX && A.fieldpos_out) {
             A.fieldpos_out[ps.idx] = (si ? kFieldIP : 0u) | (sl ? kFieldL4 | l4off : 0u);
         }
+        if constexpr (SUMS) {
+            A.sums_out[ps.idx] = ps.vals;
+        }
     }
 }
 
-template <int G, int K, bool NT, bool TX, int VER>
+template <int G, int K, bool NT, bool TX, int VER, bool SUMS = false>
 __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const PktBatchArgs& A, uint32_t idx, bool valid,
                                                 int lane, int gbase) {
     // One sum over [lead, lead + end) (end = transport end, or the IP header end when the transport
@@ -456,9 +478,16 @@ __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const Pkt
     const uint32_t d0 = pkt_dword(st.v[0], lead, 0u, gbase);
     const uint32_t d1 = pkt_dword(st.v[0], lead, 4u, gbase);
     const bool is6 = (VER == 6) || (VER == 0 && ((d0 >> 4) & 0xFu) == 6u);
-    PktInfo p = is6 ? pkt_parse_v6<G, TX>(st.v[0], lead, st.avail, gbase, A.udp_tx_csum, d0, d1)
+    PktInfo p = is6 ? pkt_parse_v6<G, TX, SUMS>(st.v[0], lead, st.avail, gbase, A.udp_tx_csum, d0, d1)
                    : pkt_parse<TX>(st.v[0], lead, st.avail, gbase, A.udp_tx_csum, d0, d1);
-    const uint32_t end = p.check_l4 ? p.l4_end : p.hlen;
+    // SUMS: a fragment's payload [hlen, l4_end) is summed as a transport part is
+    uint32_t frag_len = 0u;
+    if constexpr (SUMS) {
+        if (p.flags & F_FRAGMENT) {
+            frag_len = is6 ? p.frag_len : p.l4_end - p.hlen;
+        }
+    }
+    const uint32_t end = (p.check_l4 || frag_len != 0u) ? p.l4_end : p.hlen;
     const uint32_t rend = lead + end;
     const uint32_t nch = (rend + 15u) >> 4;
     const uint32_t cl = nch - 1u;                                // chunk holding byte rend - 1 (~0u: none)
@@ -548,6 +577,9 @@ __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const Pkt
     PktStore ps;
     ps.a = st.a;
     ps.vals = (cip & 0xFFFFu) | ((cl4 & 0xFFFFu) << 16);
+    if constexpr (SUMS) {                                        // sl4: the payload's folded sum (no pseudo-header)
+        ps.vals = frag_len != 0u ? (sl4 & 0xFFFFu) | (frag_len << 16) : (p.frag_walk ? kFragSumWalk : 0u);
+    }
     const uint32_t low = TX ? (p.l4_csum_off & 0xFFFFu) : rx_action(f, p.proto, is6, A.rx_cfg);
     ps.meta = low | ((f & 0xFFu) << 16) | (cip != ~0u ? 1u << 24 : 0u) |
               (cl4 != ~0u ? 1u << 25 : 0u) | ((valid && lane == 0) ? 1u << 26 : 0u);
@@ -569,7 +601,7 @@ __device__ __forceinline__ void pkt_desc(const PktBatchArgs& A, uint32_t i, uint
 
 // 4 waves per SIMD: the Tx instantiations otherwise take 131 VGPRs (3 waves), 25 % less memory
 // parallelism than Rx (122 VGPRs); capped at 128 they do not spill (profiles/r1txp_pmc.json).
-template <int G, int K, bool VARLEN, bool NT, bool TX, int VER>
+template <int G, int K, bool VARLEN, bool NT, bool TX, int VER, bool SUMS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) pkt_batch_kernel(PktBatchArgs A) {
     static_assert(G >= 8, "header extraction needs the first 6 chunks in slot 0");
     const int lane = (int)(threadIdx.x & (G - 1));
@@ -607,20 +639,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) p
         v1 = j + 1u < cnt;
         pkt_desc<VARLEN>(A, nx, off, avail);
         pkt_issue<G, K, NT>(S1, v1 ? base + off : z, v1 ? avail : 0u, lane);
-        pkt_store<G, TX, !VARLEN>(pend, A);                      // previous packet's stores, after the loads
+        pkt_store<G, TX, !VARLEN, SUMS>(pend, A);                // previous packet's stores, after the loads
         pin_chunks<K>(S0.v);
-        pend = pkt_consume<G, K, NT, TX, VER>(S0, A, i, v0, lane, gbase);
+        pend = pkt_consume<G, K, NT, TX, VER, SUMS>(S0, A, i, v0, lane, gbase);
         i = nx;
         nx = i + step;
         v0 = j + 2u < cnt;
         pkt_desc<VARLEN>(A, nx, off, avail);
         pkt_issue<G, K, NT>(S0, v0 ? base + off : z, v0 ? avail : 0u, lane);
-        pkt_store<G, TX, !VARLEN>(pend, A);
+        pkt_store<G, TX, !VARLEN, SUMS>(pend, A);
         pin_chunks<K>(S1.v);
-        pend = pkt_consume<G, K, NT, TX, VER>(S1, A, i, v1, lane, gbase);
+        pend = pkt_consume<G, K, NT, TX, VER, SUMS>(S1, A, i, v1, lane, gbase);
         i = nx;
     }
-    pkt_store<G, TX, !VARLEN>(pend, A);
+    pkt_store<G, TX, !VARLEN, SUMS>(pend, A);
 }
 
 template <int G, int K, bool VARLEN, bool TX, int VER>
@@ -633,6 +665,17 @@ hipError_t launch_pkt_gk(const PktBatchArgs& a, const LaunchCfg& c, hipStream_t 
     } else {
         grid = c.grid > 0 ? c.grid : (int)(((uint64_t)a.n + gpb - 1u) / gpb);
     }
+    if constexpr (!TX && VER == 0) {                             // fragment payload sums (RxBurstSums)
+        if (a.sums_out != nullptr) {
+            if (c.nt) {
+                hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, true, TX, VER, true>), dim3(grid), dim3(256), 0, s, a);
+            } else {
+                hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, false, TX, VER, true>), dim3(grid), dim3(256), 0, s, a);
+            }
+            return hipGetLastError();
+        }
+    }
+    if (!TX && a.sums_out != nullptr) return hipErrorInvalidValue;   // (one IP version: no such instantiation)
     if (c.nt) {
         hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, true, TX, VER>), dim3(grid), dim3(256), 0, s, a);
     } else {

@@ -106,7 +106,19 @@ __device__ __forceinline__ uint32_t field_le(uint32_t b0, uint32_t b1, bool odd)
     return odd ? ((b0 << 8) + b1) : (b0 + (b1 << 8));
 }
 
-struct LanePkt {          // lane k's packet after the prologue
+// SUMS instantiations (RxBurstSums) only: a fragment's payload is streamed too (end = its total
+// length, ip_sum = the bytes before the payload), so the transport slot holds its payload sum. (A base
+// class that is empty otherwise: the other instantiations' packet state keeps its size.)
+template <bool SUMS>
+struct LaneFrag {};
+template <>
+struct LaneFrag<true> {
+    uint32_t frag_len;    // fragment payload octets (0: not a fragment, or nothing to sum)
+    bool     frag_walk;   // IPv6 fragment whose Fragment header ends past the window: the walk sums it
+};
+
+template <bool SUMS = false>
+struct LanePktT : LaneFrag<SUMS> {   // lane k's packet after the prologue
     uint32_t flags;
     uint32_t end;         // packet offset one past the bytes the stream sums (0: none)
     uint32_t ip_sum;      // IPv4: exact half-word sum of the IP header [0, hlen) (absolute LE frame);
@@ -179,10 +191,10 @@ __device__ __forceinline__ bool ipv6_ext(uint32_t nh) {
 
 // IPv6 parse of pkt_parse_v6 from the lane's own window (RFC 8200; net_ipv6.c:8290-8360, 8601,
 // 5682; net_tcp.c:7871-7879; net_udp.c:1947-1957; net_icmpv6.c:2910-2948).
-template <bool TX>
-__device__ __forceinline__ LanePkt lane_parse6(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
+template <bool TX, bool SUMS = false>
+__device__ __forceinline__ LanePktT<SUMS> lane_parse6(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
                                                uint32_t avail, bool odd, uint32_t udp_mode, uint32_t d0, uint32_t d1) {
-    LanePkt p{};
+    LanePktT<SUMS> p{};
     p.l4_csum_off = ~0u;
     p.v6 = true;
     const uint32_t tot = 40u + be16(d1, 0);
@@ -217,6 +229,19 @@ __device__ __forceinline__ LanePkt lane_parse6(const uint32_t (&wd)[24], const u
     }
     if (nh == 44u) {
         p.flags = NETCSUM_PKT_FRAGMENT;
+        if constexpr (SUMS) {
+            // the payload: the octets after the 8-B Fragment header, [off + 8, tot); the stream total
+            // of [0, tot) less everything before it, which the window holds (else: the walk pass)
+            if (off + 8u < tot) {
+                if (off + 8u <= window) {
+                    p.end = tot;
+                    p.ip_sum = win_prefix(h, lead, off + 8u);
+                    p.frag_len = tot - (off + 8u);
+                } else {
+                    p.frag_walk = true;
+                }
+            }
+        }
         return p;
     }
     if (ipv6_ext(nh) || (off != 40u && off + 24u > window)) {
@@ -299,10 +324,10 @@ __device__ __forceinline__ LanePkt lane_parse6(const uint32_t (&wd)[24], const u
 }
 
 // IPv4 parse of pkt_parse (netcsum_packets.hip) from the lane's own window; `avail` bytes present.
-template <bool TX>
-__device__ __forceinline__ LanePkt lane_parse(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
+template <bool TX, bool SUMS = false>
+__device__ __forceinline__ LanePktT<SUMS> lane_parse(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
                                               uint32_t avail, bool odd, uint32_t udp_mode) {
-    LanePkt p{};
+    LanePktT<SUMS> p{};
     p.l4_csum_off = ~0u;
     const uint32_t d0 = pkt_dword_fixed<0>(wd, lead);
     const uint32_t d1 = pkt_dword_fixed<4>(wd, lead);
@@ -336,6 +361,10 @@ __device__ __forceinline__ LanePkt lane_parse(const uint32_t (&wd)[24], const u3
     p.end = hlen;
     if (frag != 0u) {
         p.flags = NETCSUM_PKT_FRAGMENT;
+        if constexpr (SUMS) {                                    // the payload [hlen, tot) is streamed too
+            p.end = tot;
+            p.frag_len = tot - hlen;
+        }
         return p;
     }
     const uint32_t l4len = tot - hlen;
@@ -404,18 +433,18 @@ __device__ __forceinline__ void store_field(uint8_t* p, uint32_t v) {    // memc
 
 // REC (Tx only): instead of writing the checksum fields, write one PktTxRecord per packet (dense,
 // coalesced); pkt_scatter_kernel then writes the fields in a pass of its own.
-template <int VER, bool TX>
-__device__ __forceinline__ LanePkt lane_parse_ver(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
+template <int VER, bool TX, bool SUMS = false>
+__device__ __forceinline__ LanePktT<SUMS> lane_parse_ver(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
                                                   uint32_t avail, bool odd, uint32_t udp_mode) {
     if constexpr (VER == 4) {
-        return lane_parse<TX>(wd, h, lead, avail, odd, udp_mode);
+        return lane_parse<TX, SUMS>(wd, h, lead, avail, odd, udp_mode);
     } else {
         const uint32_t d0 = pkt_dword_fixed<0>(wd, lead);
         const uint32_t d1 = pkt_dword_fixed<4>(wd, lead);
         if (VER == 6 || ((d0 >> 4) & 0xFu) == 6u) {
-            return lane_parse6<TX>(wd, h, lead, avail, odd, udp_mode, d0, d1);
+            return lane_parse6<TX, SUMS>(wd, h, lead, avail, odd, udp_mode, d0, d1);
         }
-        return lane_parse<TX>(wd, h, lead, avail, odd, udp_mode);
+        return lane_parse<TX, SUMS>(wd, h, lead, avail, odd, udp_mode);
     }
 }
 
@@ -476,7 +505,11 @@ __device__ __forceinline__ uint32_t piece_prefix_t(u32x4 v, uint32_t s4, uint32_
 // One wave run: packets s_begin .. s_begin + nres - 1, lane k's packet at run-relative offset prel
 // (from O, 128-B aligned) with `avail` bytes present; the run's bytes [O, O + span). VL: per-packet
 // starts (offset/length descriptors) instead of a stride.
-template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL>
+// SUMS (Rx, RxBurstSums): a fragment's payload is streamed as a transport part is and its folded sum
+// and length stored per packet (A.sums_out), 0 for every other packet; an IPv6 fragment the lane
+// cannot sum (its Fragment header ends past the window, or sits behind option headers: EXT_HDR) is
+// finished by the walk, which then writes the packet's record too.
+template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL, bool SUMS = false>
 __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec, uint32_t w, uint32_t lane,
                                         uint32_t s_begin, uint32_t nres, uintptr_t O, uint32_t prel, uint32_t avail,
                                         uint32_t span) {
@@ -511,7 +544,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
         wd[4 * c + 3] = h[c].w;
     }
     const bool odd = (prel & 1u) != 0u;                        // O is 128-B aligned
-    const LanePkt pk = lane_parse_ver<VER, TX>(wd, h, plead, avail, odd, A.udp_tx_csum);
+    const LanePktT<SUMS> pk = lane_parse_ver<VER, TX, SUMS>(wd, h, plead, avail, odd, A.udp_tx_csum);
     const uint32_t end_v = mine ? pk.end : 0u;
     // Live forms: datagrams whose summed bytes lie inside the lane's window (40-B ACKs; nothing to
     // sum) are summed here from the window: the stream neither marks their sectors nor walks their
@@ -717,6 +750,9 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
     }
     const uint32_t idx = s_begin + lane;
     need = walk_here && (f & NETCSUM_PKT_EXT_HDR) != 0u;               // walk_one writes its verdict
+    if constexpr (SUMS) {
+        need = need || (walk_here && pk.frag_walk);
+    }
     if (A.defer_word != nullptr && (f & NETCSUM_PKT_EXT_HDR)) {
         *A.defer_word = A.defer_tag;                             // the walk pass has work (benign race)
     }
@@ -734,6 +770,12 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
     if (!TX && A.action_out && !need) {
         A.action_out[idx] = (uint8_t)rx_action(f, pk.proto, pk.v6, A.rx_cfg);
     }
+    if constexpr (SUMS) {
+        // the run's records, one coalesced dword store: sl4 is the payload's folded sum (no pseudo-header)
+        if (!need) {
+            A.sums_out[idx] = pk.frag_len != 0u ? (sl4 & 0xFFFFu) | (pk.frag_len << 16) : 0u;
+        }
+    }
     if constexpr (TX) {
         uint8_t* p = reinterpret_cast<uint8_t*>(O + prel);
         if (cip != ~0u) {
@@ -750,7 +792,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
     }
     if constexpr (kWalkHere) {
         if (walk_here) {
-            v6walk::walk_wave<TX>(A, s_begin, need, lane);
+            v6walk::walk_wave<TX, SUMS>(A, s_begin, need, lane);
         }
     }
 }
@@ -760,7 +802,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
 // 128-B line (the live-piece bitmap's reach); any other run is done one datagram at a time, each as
 // a run of its own (correct for any order or overlap, at one prologue per datagram).
 // Run `run` (packets run * spw ...) by wave w of its block.
-template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL, bool DEFER = false>
+template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL, bool DEFER = false, bool SUMS = false>
 __device__ __forceinline__ void pkt_stream_run(const PktBatchArgs& A, uint32_t spw, PktTxRecord* rec, uint64_t run,
                                                uint32_t w, uint32_t lane) {
     // (offset/length runs: the live-piece forms 1 / 2; a datagram past the bitmap's reach streams its
@@ -777,8 +819,8 @@ __device__ __forceinline__ void pkt_stream_run(const PktBatchArgs& A, uint32_t s
         const uintptr_t O = a_first & ~(uintptr_t)127;
         const uint32_t lead0 = (uint32_t)(a_first - O);
         const uint32_t st = (uint32_t)A.stride;
-        pkt_run<D, NT, TX, REC, VER, BND, VL>(A, rec, w, lane, s_begin, nres, O, lead0 + lane * st, A.len_u,
-                                             lead0 + (nres - 1u) * st + A.len_u);
+        pkt_run<D, NT, TX, REC, VER, BND, VL, SUMS>(A, rec, w, lane, s_begin, nres, O, lead0 + lane * st, A.len_u,
+                                                   lead0 + (nres - 1u) * st + A.len_u);
     } else {
         const bool mine = lane < nres;
         const uint64_t off = A.off[mine ? s_begin + lane : s_begin];
@@ -794,8 +836,8 @@ __device__ __forceinline__ void pkt_stream_run(const PktBatchArgs& A, uint32_t s
                                   (lane == 0u || (uint64_t)prev_end_lo <= rel));
         if (__builtin_amdgcn_ballot_w64(!ok) == 0u) {
             const uint32_t span = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)end, (int)(nres - 1u));
-            pkt_run<D, NT, TX, REC, VER, BND, VL>(A, rec, w, lane, s_begin, nres, O, mine ? (uint32_t)rel : 0u,
-                                                 len, span);
+            pkt_run<D, NT, TX, REC, VER, BND, VL, SUMS>(A, rec, w, lane, s_begin, nres, O, mine ? (uint32_t)rel : 0u,
+                                                       len, span);
         } else if (DEFER) {
             // any other run (unordered, overlapping, far apart, or a datagram past the bitmap's reach)
             // is flagged for the deferred pass (pkt_vl_deferred_kernel): done here, one datagram at a
@@ -819,7 +861,7 @@ __device__ __forceinline__ void pkt_stream_run(const PktBatchArgs& A, uint32_t s
                 const uint32_t lk = (uint32_t)__builtin_amdgcn_readlane((int)len, (int)k);
                 const uintptr_t Ok = ((uintptr_t)A.base + ok_) & ~(uintptr_t)127;
                 const uint32_t pk = (uint32_t)((uintptr_t)A.base + ok_ - Ok);
-                pkt_run<D, NT, TX, REC, VER, BND, VL>(A, rec, w, lane, s_begin + k, 1u, Ok, pk, lk, pk + lk);
+                pkt_run<D, NT, TX, REC, VER, BND, VL, SUMS>(A, rec, w, lane, s_begin + k, 1u, Ok, pk, lk, pk + lk);
             }
         }
     }
@@ -832,7 +874,7 @@ __device__ __forceinline__ void pkt_stream_run(const PktBatchArgs& A, uint32_t s
 // the ring's plan found its descriptors in order (a run listed anyway, e.g. where the ring wraps, is
 // still done), one per 4 runs up to 2048 otherwise (the ring's first batch, reordered rings, runs
 // asked for that outgrow the reach).
-template <int D, bool NT, bool TX, bool REC, int VER, int BND>
+template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool SUMS = false>
 __global__ void __launch_bounds__(256) pkt_vl_deferred_kernel(PktBatchArgs A, uint32_t spw, PktTxRecord* rec) {
     __shared__ uint32_t s_last;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -871,8 +913,8 @@ __global__ void __launch_bounds__(256) pkt_vl_deferred_kernel(PktBatchArgs A, ui
             const uint32_t m = max(cut ? (uint32_t)__builtin_ctzll(cut) : 64u, 1u);
             const uint32_t span = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)end, (int)(m - 1u));
             const bool in = lane < m;
-            pkt_run<D, NT, TX, REC, VER, BND, true>(A, rec, w, lane, s_begin + k0, m, O, in ? (uint32_t)rel : 0u,
-                                                    in ? len : 0u, span);
+            pkt_run<D, NT, TX, REC, VER, BND, true, SUMS>(A, rec, w, lane, s_begin + k0, m, O, in ? (uint32_t)rel : 0u,
+                                                          in ? len : 0u, span);
             k0 += m;
         }
     }
@@ -1015,7 +1057,7 @@ __global__ void __launch_bounds__(256) pkt_plan_kernel(PktBatchArgs A) {
 // done inline, one datagram at a time (false: the kernel then carries that loop, 79-93 VGPRs, 5-6 waves
 // per SIMD — the residency the dense offset/length rings want anyway, so their ring plan takes this
 // form and no deferred pass; profiles/r5g_ring_probe_grid.jsonl).
-template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL, bool DEF = VL>
+template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool VL, bool DEF = VL, bool SUMS = false>
 __global__ void __launch_bounds__(256) pkt_stream_kernel(PktBatchArgs A, uint32_t spw, PktTxRecord* rec) {
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t bid = blockIdx.x, nblk = gridDim.x;
@@ -1028,7 +1070,7 @@ __global__ void __launch_bounds__(256) pkt_stream_kernel(PktBatchArgs A, uint32_
         nblk -= 1u;
     }
     const uint32_t blk = A.xcd ? xcd_block(bid, nblk) : bid;
-    pkt_stream_run<D, NT, TX, REC, VER, BND, VL, DEF>(A, spw, rec, (uint64_t)blk * 4u + w, w, threadIdx.x & 63u);
+    pkt_stream_run<D, NT, TX, REC, VER, BND, VL, DEF, SUMS>(A, spw, rec, (uint64_t)blk * 4u + w, w, threadIdx.x & 63u);
 }
 
 // Second pass of the two-pass Tx: one thread per packet writes its fields (and flags) from its record.
@@ -1318,17 +1360,17 @@ hipError_t launch_tx_flush(hipStream_t s) {
 thread_local bool tls_fault_skip_deferred = false;
 
 // the deferred pass, unless a test asked for its launch to fail (set_fault_skip_deferred)
-template <int D, bool NT, bool TX, bool REC, int VER, int BND>
+template <int D, bool NT, bool TX, bool REC, int VER, int BND, bool SUMS = false>
 hipError_t launch_vl_deferred(const PktBatchArgs& a, int dgrid, uint32_t spw, PktTxRecord* rec, hipStream_t s) {
     if (tls_fault_skip_deferred) {
         tls_fault_skip_deferred = false;
         return hipErrorLaunchFailure;
     }
-    hipLaunchKernelGGL((pkt_vl_deferred_kernel<D, NT, TX, REC, VER, BND>), dim3(dgrid), dim3(256), 0, s, a, spw, rec);
+    hipLaunchKernelGGL((pkt_vl_deferred_kernel<D, NT, TX, REC, VER, BND, SUMS>), dim3(dgrid), dim3(256), 0, s, a, spw, rec);
     return hipGetLastError();
 }
 
-template <int D, bool NT, bool TX, int VER, int BND, bool VL>
+template <int D, bool NT, bool TX, int VER, int BND, bool VL, bool SUMS = false>
 hipError_t launch_pkt_stream_t(const PktBatchArgs& a0, uint32_t spw, hipStream_t s, PktTxRecord* rec, bool scatter) {
     PktBatchArgs a = a0;
     // no piece touch by default: the header prologue already loads each packet's first bytes with
@@ -1358,14 +1400,14 @@ hipError_t launch_pkt_stream_t(const PktBatchArgs& a0, uint32_t spw, hipStream_t
         return e != hipSuccess ? e : launch_tx_flush(s);
     }
     if (VL && a.vl_ctr == nullptr) {
-        hipLaunchKernelGGL((pkt_stream_kernel<D, NT, TX, false, VER, BND, VL, false>), dim3(grid), dim3(256), lds, s, a, spw, rec);
+        hipLaunchKernelGGL((pkt_stream_kernel<D, NT, TX, false, VER, BND, VL, false, SUMS>), dim3(grid), dim3(256), lds, s, a, spw, rec);
     } else {
-        hipLaunchKernelGGL((pkt_stream_kernel<D, NT, TX, false, VER, BND, VL>), dim3(grid), dim3(256), lds, s, a, spw, rec);
+        hipLaunchKernelGGL((pkt_stream_kernel<D, NT, TX, false, VER, BND, VL, VL, SUMS>), dim3(grid), dim3(256), lds, s, a, spw, rec);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && VL && a.vl_ctr != nullptr) {
         if constexpr (VL) {
-            e = launch_vl_deferred<D, NT, TX, false, VER, BND>(a, dgrid, spw, rec, s);
+            e = launch_vl_deferred<D, NT, TX, false, VER, BND, SUMS>(a, dgrid, spw, rec, s);
         }
     }
     return (e != hipSuccess || !TX) ? e : launch_tx_flush(s);
@@ -1445,6 +1487,19 @@ hipError_t launch_pkt_stream(const PktBatchArgs& a, int ip_ver, int depth, uint3
         }
     }
     const bool vl = a.off != nullptr;
+    // fragment payload sums (a.sums_out): the SUMS instantiations, Rx of mixed batches only
+    if (!tx && a.sums_out != nullptr) {
+        if (ip_ver != 0 || rec != nullptr) return hipErrorInvalidValue;
+#define NETCSUM_PS(D_, B_, VL_)                                                                           \
+    if (depth == D_ && bound == B_ && vl == VL_)                                                          \
+        return nt ? launch_pkt_stream_t<D_, true, false, 0, B_, VL_, true>(a, spw, s, nullptr, false)     \
+                  : launch_pkt_stream_t<D_, false, false, 0, B_, VL_, true>(a, spw, s, nullptr, false);
+        NETCSUM_PS(4, 0, false) NETCSUM_PS(4, 1, false) NETCSUM_PS(4, 2, false) NETCSUM_PS(4, 3, false)
+        NETCSUM_PS(8, 0, false) NETCSUM_PS(8, 2, false) NETCSUM_PS(8, 3, false)
+        NETCSUM_PS(4, 1, true) NETCSUM_PS(4, 2, true) NETCSUM_PS(8, 2, true)
+#undef NETCSUM_PS
+        return hipErrorInvalidValue;
+    }
     // every bound with 4 pieces in flight, 8 with bounds 0, 2 and 3; offset/length runs in the
     // live-piece forms 1 and 2
 #define NETCSUM_P(V_, D_, NT_, TX_, B_, VL_)                                                              \

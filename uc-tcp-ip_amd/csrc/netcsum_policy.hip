@@ -272,7 +272,11 @@ NET_ERR pkt_decide(const Tune& t, const PktJob& j, PktPlan& p) {
     a.udp_tx_csum = j.udp_mode;
     a.action_out = tx ? nullptr : j.action;
     a.rx_cfg = j.rx_cfg;
-    a.fieldpos_out = tx ? j.fieldpos : nullptr;
+    if (tx) {
+        a.fieldpos_out = j.fieldpos;
+    } else {
+        a.sums_out = reinterpret_cast<uint32_t*>(j.sums);
+    }
     netcsum::LaunchCfg& c = p.c;
     const uint32_t chunks = j.off ? 288u : ((uint32_t)j.pkt_len + 30u) / 16u;
     int g = t.group;
@@ -404,8 +408,9 @@ void pkt_settle(const Tune& t, const PktJob& j, PktPlan& p) {
             p.spw = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(p.spw, cap));
         }
     }
-    snprintf(p.desc, sizeof p.desc, "pkt_stream_kernel<D=%d%s,%s,%s> block=256 pkts_per_wave=%u bound=%d%s%s%s%s%s", p.d,
-             p.snt ? ",nt" : "", j.tx ? "tx" : "rx", j.ip_ver == 4 ? "v4" : j.ip_ver == 6 ? "v6" : "mixed", p.spw, p.bound,
+    snprintf(p.desc, sizeof p.desc, "pkt_stream_kernel<D=%d%s,%s,%s%s> block=256 pkts_per_wave=%u bound=%d%s%s%s%s%s", p.d,
+             p.snt ? ",nt" : "", j.tx ? "tx" : "rx", j.ip_ver == 4 ? "v4" : j.ip_ver == 6 ? "v6" : "mixed",
+             !j.tx && p.a.sums_out ? ",sums" : "", p.spw, p.bound,
              j.off ? (p.vl_inline ? " offlen (inline fallback)" : " offlen +pkt_vl_deferred_kernel") : "",
              p.two ? " +pkt_scatter_kernel" : "", p.walk ? " +inline_v6_walk" : "", p.plan_note, p.ahead_note);
 }

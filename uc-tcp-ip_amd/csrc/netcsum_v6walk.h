@@ -78,7 +78,9 @@ __device__ __forceinline__ uint32_t group_sum(const uint8_t* p, uint32_t lo, uin
 }
 
 // A lane group finishes datagram i (all values below are uniform in the group; lane = its lane).
-template <bool TX>
+// SUMS (Rx, RxBurstSums): the group also writes the datagram's NETCSUM_FRAG_SUM record (A.sums_out): a
+// fragment's payload [Fragment header end, tot) by the same group sum, 0 for anything else.
+template <bool TX, bool SUMS = false>
 __device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint32_t lane) {
     uint64_t off64;
     uint32_t avail;
@@ -120,12 +122,19 @@ __device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint
         off += eh_len;
     }
     uint32_t csum_off = ~0u;
+    uint32_t frag_rec = 0u;                         // SUMS: sum | len << 16
     bool pseudo = false, check = false;
     if (f == 0u) {
         f = W_IP_OK;
         const uint32_t ulen = tot - off;
         if (nh == 44u) {
             f |= W_FRAGMENT;
+            if constexpr (SUMS) {
+                if (ulen > 8u) {                    // octets after the 8-B Fragment header
+                    // group_sum folds big-endian half-words; the record holds the host-order value
+                    frag_rec = rot8(group_sum(p, off + 8u, tot, ~0u, lane)) | ((ulen - 8u) << 16);
+                }
+            }
         } else if (ext_hdr_value(nh)) {
             f |= W_EXT_HDR;
         } else if (nh == 6u) {
@@ -193,13 +202,16 @@ __device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint
         if (!TX && A.action_out) {
             A.action_out[i] = (uint8_t)rx_action(f, nh, true, A.rx_cfg);
         }
+        if constexpr (SUMS) {
+            A.sums_out[i] = frag_rec;
+        }
     }
 }
 
 
 // The calling wave's datagrams s0 + k whose lane k has `need` set, four at a time by its 16-lane
 // groups (every lane of the wave must be active).
-template <bool TX>
+template <bool TX, bool SUMS = false>
 __device__ __forceinline__ void walk_wave(const PktBatchArgs& A, uint32_t s0, bool need, uint32_t lane) {
     const uint32_t grp = lane / kLanes;
     uint64_t m = __ballot(need);                    // wave-uniform
@@ -213,7 +225,7 @@ __device__ __forceinline__ void walk_wave(const PktBatchArgs& A, uint32_t s0, bo
             }
         }
         if (j != ~0u) {
-            walk_one<TX>(A, s0 + j, lane % kLanes);
+            walk_one<TX, SUMS>(A, s0 + j, lane % kLanes);
         }
     }
 }

@@ -42,7 +42,9 @@ namespace {
 // 16-flags-per-lane scan read the flags no faster: 4.8 us per 1 M either way, profiles/r2zt_*), and
 // the wave's four 16-lane groups take the next four flagged datagrams at a time (their dependent
 // chain loads overlap).
-template <bool TX>
+// SUMS (Rx, RxBurstSums): a fragment the batch kernel could not sum carries kFragSumWalk in its record
+// and is walked too; every walked datagram's record is written by its group.
+template <bool TX, bool SUMS = false>
 __global__ void __launch_bounds__(256) pkt_v6_walk_kernel(PktBatchArgs A) {
     if (A.defer_word != nullptr && *A.defer_word != A.defer_tag) {
         return;                                     // no batch kernel deferred a datagram this call
@@ -50,8 +52,11 @@ __global__ void __launch_bounds__(256) pkt_v6_walk_kernel(PktBatchArgs A) {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint64_t w0 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); w0 < A.n; w0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t i = w0 + lane;
-        const bool need = i < A.n && (A.flags_out[i] & v6walk::W_EXT_HDR) != 0u;
-        v6walk::walk_wave<TX>(A, (uint32_t)w0, need, lane);
+        bool need = i < A.n && (A.flags_out[i] & v6walk::W_EXT_HDR) != 0u;
+        if constexpr (SUMS) {
+            need = need || (i < A.n && A.sums_out[i] == kFragSumWalk);
+        }
+        v6walk::walk_wave<TX, SUMS>(A, (uint32_t)w0, need, lane);
     }
 }
 
@@ -62,7 +67,9 @@ hipError_t launch_pkt_v6_walk(const PktBatchArgs& a, bool tx, int cus, hipStream
     if (a.flags_out == nullptr) return hipErrorInvalidValue;
     const uint64_t blocks = ((uint64_t)a.n + 255u) / 256u;
     const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1) * 64u);
-    if (tx) {
+    if (!tx && a.sums_out != nullptr) {
+        hipLaunchKernelGGL((pkt_v6_walk_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
+    } else if (tx) {
         hipLaunchKernelGGL(pkt_v6_walk_kernel<true>, dim3(grid), dim3(256), 0, s, a);
     } else {
         hipLaunchKernelGGL(pkt_v6_walk_kernel<false>, dim3(grid), dim3(256), 0, s, a);

@@ -245,6 +245,14 @@ def lib() -> ctypes.CDLL:
     L.NetUtil_MI355X_RxValidateIPHost.restype = i32
     L.NetUtil_MI355X_TxFinalizeIPHost.argtypes = [vp, vp, vp, u64, u16, u32, vp, i32, u32]
     L.NetUtil_MI355X_TxFinalizeIPHost.restype = i32
+    L.NetUtil_MI355X_RxBurstSums.argtypes = [vp, vp, vp, u64, u16, u32, u32, vp, vp, vp, vp]
+    L.NetUtil_MI355X_RxBurstSums.restype = i32
+    L.NetUtil_MI355X_RxBurstSumsHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, vp, vp, vp, u32]
+    L.NetUtil_MI355X_RxBurstSumsHost.restype = i32
+    L.NetUtil_MI355X_FragSumCalc.argtypes = [vp, u32, vp, u16, ctypes.POINTER(ctypes.c_uint16)]
+    L.NetUtil_MI355X_FragSumCalc.restype = i32
+    L.NetUtil_MI355X_FragSumVerify.argtypes = [vp, u32, vp, u16, ctypes.POINTER(ctypes.c_uint8)]
+    L.NetUtil_MI355X_FragSumVerify.restype = i32
     L.NetUtil_MI355X_RxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, vp, vp, u32]
     L.NetUtil_MI355X_RxBurstHost.restype = i32
     L.NetUtil_MI355X_TxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, vp, u32]
@@ -577,6 +585,50 @@ def rx_burst(base, n, action, flags=None, off=None, lens=None, stride=0, pkt_len
     return err
 
 
+def rx_burst_sums(base, n, action, sums, flags=None, off=None, lens=None, stride=0, pkt_len=0, rx_cfg=0, stream=None,
+                  check=True):
+    """NetUtil_MI355X_RxBurstSums: rx_burst plus one NETCSUM_FRAG_SUM {u16 sum, u16 len} per frame in
+    `sums` (4 B per frame, e.g. an int32 tensor of n elements): a fragment's payload sum and length."""
+    _pkt_bounds(base, off, lens, stride, pkt_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(sums, 4 * n, "fragment sums")
+    err = lib().NetUtil_MI355X_RxBurstSums(_p(base), _p(off), _p(lens), stride, pkt_len, n, rx_cfg, _p(action),
+                                           _p(flags), _p(sums), _stream(stream))
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstSums")
+    return err
+
+
+def _frag_records(frags):
+    """[(sum, len), ...] or a uint16 array of n x 2 -> (contiguous uint16 array n x 2, n)."""
+    import numpy as np
+    a = np.ascontiguousarray(frags, dtype=np.uint16).reshape(-1, 2)
+    return a, a.shape[0]
+
+
+def frag_sum_calc(frags, pseudo=None):
+    """NetUtil_MI355X_FragSumCalc (host logic): the DataCalc value of the datagram whose fragments, in
+    reassembly order, have the records `frags` ((sum, len) pairs), with pseudo-header bytes `pseudo`
+    -> (checksum, NET_ERR)."""
+    a, n = _frag_records(frags)
+    ph = HostBytes(pseudo) if pseudo is not None else None
+    out = ctypes.c_uint16(0)
+    err = lib().NetUtil_MI355X_FragSumCalc(a.ctypes.data if n else None, n, ph.ptr if ph else None, ph.len if ph else 0,
+                                           ctypes.byref(out))
+    return int(out.value), int(err)
+
+
+def frag_sum_verify(frags, pseudo=None):
+    """NetUtil_MI355X_FragSumVerify (host logic) -> (DEF_OK / DEF_FAIL, NET_ERR)."""
+    a, n = _frag_records(frags)
+    ph = HostBytes(pseudo) if pseudo is not None else None
+    out = ctypes.c_uint8(0)
+    err = lib().NetUtil_MI355X_FragSumVerify(a.ctypes.data if n else None, n, ph.ptr if ph else None,
+                                             ph.len if ph else 0, ctypes.byref(out))
+    return int(out.value), int(err)
+
+
 def tx_burst(base, n, flags=None, off=None, lens=None, stride=0, pkt_len=0, stream=None, check=True):
     """NetUtil_MI355X_TxBurst: fill in the checksum fields the stack left to the offload, in place."""
     _pkt_bounds(base, off, lens, stride, pkt_len, n, flags)
@@ -650,6 +702,20 @@ def rx_burst_host(base, n, action, flags=None, off=None, lens=None, stride=0, pk
                                            _p(flags), n_chunks)
     if check:
         _check(err, "NetUtil_MI355X_RxBurstHost")
+    return err
+
+
+def rx_burst_sums_host(base, n, action, sums, flags=None, off=None, lens=None, stride=0, pkt_len=0, rx_cfg=0,
+                       n_chunks=0, check=True):
+    """NetUtil_MI355X_RxBurstSumsHost: rx_burst_host plus the per-frame fragment sums (host arrays)."""
+    _pkt_bounds(base, off, lens, stride, pkt_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(sums, 4 * n, "fragment sums")
+    err = lib().NetUtil_MI355X_RxBurstSumsHost(_p(base), _p(off), _p(lens), stride, pkt_len, n, rx_cfg, _p(action),
+                                               _p(flags), _p(sums), n_chunks)
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstSumsHost")
     return err
 
 
