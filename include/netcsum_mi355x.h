@@ -449,6 +449,110 @@ NET_ERR  NetUtil_MI355X_FragSumVerify      (const NETCSUM_FRAG_SUM *frag,
                                             CPU_BOOLEAN     *p_ok);
 
 /* ============================================================================================
+ * (2b'''') Rx bursts of Ethernet frames: the 802.x demux ahead of the checksum pass.
+ *
+ * The entry points above take frames that start at the IP header. A receive ring holds whole frames:
+ * Ethernet II (IP at +14), IEEE 802.3 + 802.2 LLC + SNAP (IP at +22; the reference receives them,
+ * IF/net_if_802x.c:2038-2050, :2246-2362), ARP, types the stack does not know, runts, frames for
+ * other stations. RxBurstEther classifies each frame as NetIF_802x_Rx / NetIF_802x_RxPktFrameDemux do
+ * (the rules, stated once for kernel and host: netcsum_ether.h), finds the IP datagram where they
+ * would, and runs RxBurst on those datagrams; d_l2[i] is the frame's class, NETCSUM_L2_* below, so the
+ * driver's tally (RxBurstEtherTally) matches Net_ErrCtrs.IFs.IFs_802x.
+ *
+ * Frames: frame i starts at d_base + d_off[i] (d_off non-NULL) or d_base + i * stride, any alignment,
+ * and has d_len[i] (d_len non-NULL) or frame_len octets received (the reference's TotLen). d_off ==
+ * NULL with d_len != NULL is allowed here — slots at a fixed pitch with per-frame received lengths is
+ * what a descriptor ring gives (IF/net_if.c:6593). Whether the received length counts the 4 FCS octets
+ * is the driver's matter: the reference's own 802.3 length check assumes it does (:2268), and the rule
+ * restates that check unchanged. The FCS is not verified.
+ *
+ * Rules, in the reference's order; the first check that fails names the class:
+ *   1. len < 60 (NET_IF_802x_FRAME_MIN_SIZE): INV_FRAME_SIZE, from len alone — no octet of the frame
+ *      is read.
+ *   2. destination (:1982-2015): broadcast is accepted; a group address (bit 0 of octet 0) is accepted
+ *      with NETCSUM_ETHCFG_MCAST_RX (the stack's NET_MCAST_RX_MODULE_EN); any other destination must
+ *      equal hw_addr, else INV_ADDR_DEST. hw_addr == NULL skips the check (promiscuous).
+ *   3. source all-zero or broadcast (NetIF_802x_AddrHW_IsValid, :1024-1034, :2019-2026): INV_ADDR_SRC.
+ *   4. the big-endian word at +12 (:2037-2050): above 1500 it is an Ethernet II type (:2155-2187) —
+ *      0x0800 ETHER_IPV4, 0x86DD ETHER_IPV6, 0x0806 ETHER_ARP, anything else INV_ETHER_TYPE (1501-1535,
+ *      RARP 0x8035, 0x8100: the reference has no VLAN support); header length 14.
+ *   5. else the IEEE 802 path (:2266-2352): only if len >= 64 the length field must equal len - 18,
+ *      else INV_LEN_FRAME; DSAP 0xAA else INV_LLC_DSAP; SSAP 0xAA else INV_LLC_SSAP; Ctrl 0x03 else
+ *      INV_LLC_CTRL; the three organisation-code octets 0 else INV_SNAP_CODE; the SNAP type gives
+ *      SNAP_IPV4 / SNAP_IPV6 / SNAP_ARP by the same three values, else INV_SNAP_TYPE; header length 22.
+ *
+ * Results: for a frame of an IP class, d_action[i] / d_flags[i] are byte for byte what RxBurst writes
+ * for the datagram at frame + header length with len - header length octets present (padding and any
+ * FCS octets are trailing octets past the IP total length). A frame whose type says IPv4 with first
+ * nibble 6, or IPv6 with a first nibble other than 6, keeps its IP class and gets the verdict of a
+ * datagram of no octets, flags NETCSUM_PKT_MALFORMED / action NETCSUM_RX_DELIVER: the reference calls
+ * NetIPv4_Rx / NetIPv6_Rx by frame type and rejects on the version before any checksum. Every ARP and
+ * INV_* frame gets the same verdict: the stack's interface-layer checks are not removed by the offload
+ * flags and reject the INV_* frames, so the adapter's contract stays "dropped here iff a checksum
+ * fails".
+ *
+ * Two launches on the caller's stream: ether_demux_kernel (one lane per frame: the frame's first 23
+ * octets by aligned dword loads, the class, and an offset/length descriptor in this thread's scratch
+ * for the stream — 10 B per frame, leased as the Tx records are, with their rule under stream
+ * capture), then the offset/length RxBurst over the descriptors, unchanged. An IP frame's descriptor
+ * is {frame + 14 or 22, len - 14 or 22}; every other frame's, and a mismatch's, {frame, 0}.
+ * NetUtil_MI355X_LastLaunch() reads "ether_demux b=<blocks> | " followed by RxBurst's string.
+ *
+ * Checks before any device work: NULL d_action, d_l2 or d_base with n_frame != 0
+ * NET_ERR_FAULT_NULL_PTR; unknown rx_cfg or eth_cfg bits NET_UTIL_ERR_MI355X_INVALID_ARG; n_frame == 0
+ * succeeds without a launch. hw_addr is HOST memory (6 octets, or NULL).
+ *
+ * RxBurstEtherHost ((2e) below): the same from host memory, always by the copy pipeline.
+ * EtherClass / RxBurstEtherTally: host logic, no device work. EtherClass is the rules on one frame in
+ * host memory (*p_hdr_len, optional: 14 / 22, 0 for the INV_* classes); the tally's rules are
+ * RxBurstTally's: ctr[c] += frames of class c; NULL with n_frame != 0 NET_ERR_FAULT_NULL_PTR, a class
+ * >= NETCSUM_L2_NBR_CLASSES NET_UTIL_ERR_MI355X_INVALID_ARG (nothing counted).
+ * ============================================================================================ */
+#define NETCSUM_L2_ETHER_IPV4          0u  /* Ethernet II, IPv4 at +14                                           */
+#define NETCSUM_L2_ETHER_IPV6          1u  /* Ethernet II, IPv6 at +14                                           */
+#define NETCSUM_L2_SNAP_IPV4           2u  /* 802.3 + LLC/SNAP, IPv4 at +22                                      */
+#define NETCSUM_L2_SNAP_IPV6           3u  /* 802.3 + LLC/SNAP, IPv6 at +22                                      */
+#define NETCSUM_L2_ETHER_ARP           4u  /* Ethernet II, ARP at +14 (NetARP_Rx)                                */
+#define NETCSUM_L2_SNAP_ARP            5u  /* 802.3 + LLC/SNAP, ARP at +22                                       */
+#define NETCSUM_L2_INV_FRAME_SIZE      6u  /* discarded in NetIF_802x_Rx (:548-554)         RxInvFrameCtr        */
+#define NETCSUM_L2_INV_ADDR_DEST       7u  /* NET_IF_ERR_INVALID_ADDR_DEST  (:2009-2013)    RxInvAddrDestCtr     */
+#define NETCSUM_L2_INV_ADDR_SRC        8u  /* NET_IF_ERR_INVALID_ADDR_SRC   (:2021-2025)    RxInvAddrSrcCtr      */
+#define NETCSUM_L2_INV_ETHER_TYPE      9u  /* NET_IF_ERR_INVALID_ETHER_TYPE (:2182-2186)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_LEN_FRAME      10u  /* NET_IF_ERR_INVALID_LEN_FRAME  (:2269-2273)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_LLC_DSAP       11u  /* NET_IF_ERR_INVALID_LLC_DSAP   (:2278-2282)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_LLC_SSAP       12u  /* NET_IF_ERR_INVALID_LLC_SSAP   (:2285-2289)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_LLC_CTRL       13u  /* NET_IF_ERR_INVALID_LLC_CTRL   (:2292-2296)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_SNAP_CODE      14u  /* NET_IF_ERR_INVALID_SNAP_CODE  (:2300-2316)    RxInvFrameCtr        */
+#define NETCSUM_L2_INV_SNAP_TYPE      15u  /* NET_IF_ERR_INVALID_SNAP_TYPE  (:2347-2351)    RxInvFrameCtr        */
+#define NETCSUM_L2_NBR_CLASSES        16u
+
+#define NETCSUM_ETHCFG_MCAST_RX       0x1u  /* NET_MCAST_RX_MODULE_EN: group destinations are received           */
+
+NET_ERR  NetUtil_MI355X_RxBurstEther       (const void      *d_base,
+                                            const uint64_t  *d_off,
+                                            const uint16_t  *d_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
+                                            uint32_t         rx_cfg,
+                                            uint32_t         eth_cfg,
+                                            const uint8_t   *hw_addr,
+                                            uint8_t         *d_action,
+                                            uint8_t         *d_flags,
+                                            uint8_t         *d_l2,
+                                            void            *hip_stream);
+
+uint8_t  NetUtil_MI355X_EtherClass         (const void      *frame,
+                                            uint16_t         len,
+                                            uint32_t         eth_cfg,
+                                            const uint8_t   *hw_addr,
+                                            uint16_t        *p_hdr_len);
+
+NET_ERR  NetUtil_MI355X_RxBurstEtherTally  (const uint8_t   *h_l2,
+                                            uint32_t         n_frame,
+                                            uint32_t        *ctr);
+
+/* ============================================================================================
  * (2e) Host-memory forms (the path starts in NIC Rx buffers, IF/net_if.c:6593,
  * and socket Tx buffers, Source/net_sock.c:5531). Same arguments and results as the device forms
  * above with every pointer in HOST memory. The call splits the batch into n_chunks chunks and
@@ -523,6 +627,24 @@ NET_ERR  NetUtil_MI355X_RxBurstSumsHost    (const void      *h_base,
                                             uint8_t         *h_action,
                                             uint8_t         *h_flags,
                                             NETCSUM_FRAG_SUM *h_sums,
+                                            uint32_t         n_chunks);
+
+/* RxBurstEther ((2b'''') above) over frames in host memory — the receive ring itself, h_len the
+ * received lengths; h_off == NULL with h_len != NULL is allowed as there. Always the copy pipeline: per
+ * chunk the frames' span and descriptors go H2D, then the demux, the packet batch, and action, flags
+ * (optional) and l2 come back D2H. */
+NET_ERR  NetUtil_MI355X_RxBurstEtherHost   (const void      *h_base,
+                                            const uint64_t  *h_off,
+                                            const uint16_t  *h_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
+                                            uint32_t         rx_cfg,
+                                            uint32_t         eth_cfg,
+                                            const uint8_t   *hw_addr,
+                                            uint8_t         *h_action,
+                                            uint8_t         *h_flags,
+                                            uint8_t         *h_l2,
                                             uint32_t         n_chunks);
 
 NET_ERR  NetUtil_MI355X_TxBurstHost        (void            *h_base,

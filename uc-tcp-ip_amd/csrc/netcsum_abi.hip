@@ -827,6 +827,61 @@ NET_ERR NetUtil_MI355X_RxBurstSums(const void* d_base, const uint64_t* d_off, co
     return pkt_batch(tls_tune, j);
 }
 
+// Rx burst of Ethernet frames: the 802.x demux pass (netcsum_ether.hip) writes each frame's class and the
+// offset/length descriptor of its IP datagram into this thread's scratch for the stream, then RxBurst's
+// offset/length batch runs over the descriptors, unchanged. The lease is taken once, for both steps, and
+// ends after the packet launches: pkt_batch leases the same slot for its own scratch (Rx offset/length:
+// 256 B of words, then at most 4 B per frame of deferred-run list, or one flag byte per frame for the
+// walk pass), which fits below the descriptors, so its lease never grows the buffer under them. Under
+// stream capture the rule is the Tx records': the slot is pinned, and a capture needs one uncaptured
+// call of at least its size first.
+NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                                    CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                    const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
+                                    void* hip_stream) {
+    if (n_frame != 0 && (d_action == nullptr || d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    int dev = 0;
+    NC_HIP(hipGetDevice(&dev));
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    const size_t n = n_frame;
+    const size_t o_off = (256u + 4u * n + 16u + 255u) & ~(size_t)255u;   // past pkt_batch's own scratch
+    const size_t o_len = (o_off + 8u * n + 255u) & ~(size_t)255u;
+    ScratchLease scratch;
+    NC_HIP(scratch.acquire(dev, hs, o_len + 2u * n));
+    uint8_t* sp = static_cast<uint8_t*>(scratch.ptr());
+    netcsum::EtherDemuxArgs a{};
+    a.base = static_cast<const uint8_t*>(d_base);
+    a.off = d_off;
+    a.len = d_len;
+    a.stride = stride;
+    a.len_u = frame_len;
+    a.n = n_frame;
+    a.eth_cfg = eth_cfg;
+    if (hw_addr != nullptr) {
+        a.have_hw = 1u;
+        a.hw_lo = (uint32_t)hw_addr[0] | ((uint32_t)hw_addr[1] << 8) | ((uint32_t)hw_addr[2] << 16) | ((uint32_t)hw_addr[3] << 24);
+        a.hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
+    }
+    a.l2_out = d_l2;
+    a.off_out = reinterpret_cast<uint64_t*>(sp + o_off);
+    a.len_out = reinterpret_cast<uint16_t*>(sp + o_len);
+    NC_HIP(netcsum::launch_ether_demux(a, hs));
+    PktJob j = pkt_job(d_base, a.off_out, a.len_out, 0, 0, n_frame, d_flags, hip_stream);
+    j.action = d_action;
+    j.rx_cfg = rx_cfg;
+    const NET_ERR e = pkt_batch(tls_tune, j);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    NC_HIP(scratch.end());
+    char desc[256];
+    snprintf(desc, sizeof desc, "ether_demux b=%u | %.220s", netcsum::ether_demux_blocks(n_frame), netcsum::last_launch());
+    netcsum::set_last_launch(desc);
+    return NET_UTIL_ERR_NONE;
+}
+
 uint8_t NetUtil_MI355X_RxAction(uint8_t flags, uint8_t proto, int ipv6, uint32_t rx_cfg) {
     return (uint8_t)netcsum::rx_action(flags, proto, ipv6 != 0, rx_cfg);
 }

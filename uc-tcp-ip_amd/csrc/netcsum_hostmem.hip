@@ -1016,6 +1016,77 @@ NET_ERR NetUtil_MI355X_RxBurstSumsHost(const void* h_base, const uint64_t* h_off
     return pkt_host(h, n_chunks);
 }
 
+// RxBurstEther over frames in host memory: the copy pipeline of pkt_host_copy with the frame-level
+// descriptors (per-frame lengths also without offsets: a ring of slots) and the classes as a third
+// result. Per chunk: H2D of the frames' span and descriptors, the device form (demux, packet batch) on
+// the chunk's stream, D2H of actions, flags and classes.
+NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                        CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                        const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
+                                        uint32_t n_chunks) {
+    if (n_frame != 0 && (h_action == nullptr || h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    HostCtx* cp = nullptr;
+    NET_ERR e = host_ctx(&cp);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    HostCtx& c = *cp;
+    std::vector<HostChunk> ch;
+    uint64_t maxb = plan_chunks(nullptr, nullptr, stride, frame_len, n_frame, n_chunks == 0 ? 1u : n_chunks, ch);
+    if (h_off != nullptr || h_len != nullptr) {              // (offsets and received lengths come separately here:
+        maxb = 0;                                            // a ring of slots has lengths and no offsets)
+        for (HostChunk& k : ch) {
+            k.lo = ~0ull;
+            k.hi = 0;
+            for (uint32_t i = k.s0; i < k.s0 + k.ns; ++i) {
+                const uint64_t o = h_off ? h_off[i] : (uint64_t)i * stride;
+                k.lo = std::min<uint64_t>(k.lo, o);
+                k.hi = std::max<uint64_t>(k.hi, o + (h_len ? h_len[i] : frame_len));
+            }
+            maxb = std::max<uint64_t>(maxb, k.hi - k.lo);
+        }
+    }
+    const uint32_t per = ch[0].ns;
+    // device slot: [bytes | offsets | lengths | flags | actions | classes]; host slot: [offsets | lengths]
+    const size_t o_off = al256(maxb), o_len = o_off + al256(h_off ? (size_t)per * 8u : 0u);
+    const size_t o_fl = o_len + al256(h_len ? (size_t)per * 2u : 0u), o_act = o_fl + al256(per), o_l2 = o_act + al256(per);
+    const size_t hs_len = al256(h_off ? (size_t)per * 8u : 0u);
+    e = ensure_pipe(c, o_l2 + al256(per), hs_len + al256(h_len ? (size_t)per * 2u : 0u));
+    if (e != NET_UTIL_ERR_NONE) return e;
+    PipeDrainOnExit guard{c};
+    const uint8_t* hb = static_cast<const uint8_t*>(h_base);
+    for (size_t k = 0; k < ch.size(); ++k) {
+        const HostChunk& q = ch[k];
+        const int j = (int)(k % 3u);
+        hipStream_t st = c.pstream[j];
+        uint8_t* d = c.d_pipe[j];
+        if (k >= 3 && (h_off || h_len)) NC_HIP(hipStreamSynchronize(st));   // slot j's staging is free again
+        if (q.hi > q.lo) NC_HIP(hipMemcpyAsync(d, hb + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
+        if (h_off) {
+            uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
+            for (uint32_t i = 0; i < q.ns; ++i) h_o[i] = h_off[q.s0 + i] - q.lo;
+            NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
+        }
+        if (h_len) {
+            uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + hs_len);
+            std::memcpy(h_l, h_len + q.s0, (size_t)q.ns * 2u);
+            NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
+        }
+        e = NetUtil_MI355X_RxBurstEther(d, h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr,
+                                        h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr, stride, frame_len, q.ns,
+                                        rx_cfg, eth_cfg, hw_addr, d + o_act, h_flags ? d + o_fl : nullptr, d + o_l2, st);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
+        NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, st));
+        NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
+    }
+    for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
+    guard.done = true;
+    return NET_UTIL_ERR_NONE;
+}
+
 NET_ERR NetUtil_MI355X_TxBurstHost(void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
                                    CPU_INT16U pkt_len, uint32_t n_pkt, uint8_t* h_flags, uint32_t n_chunks) {
     PktJob h = pkt_job(h_base, h_off, h_len, stride, pkt_len, n_pkt, h_flags, nullptr);

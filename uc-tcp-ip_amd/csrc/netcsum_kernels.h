@@ -291,6 +291,27 @@ hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t
 // IPv6 extension-header chains past the batch kernels' window (flags EXT_HDR): walked to the end and
 // finished in place (netcsum_v6walk.hip); a.flags_out holds the batch kernel's flags.
 hipError_t launch_pkt_v6_walk(const PktBatchArgs& a, bool tx, int cus, hipStream_t s);
+// The 802.x demux ahead of an Rx burst of Ethernet frames (netcsum_ether.hip ether_demux_kernel; the
+// rules: include/netcsum_ether.h): per frame its layer-2 class and the offset/length descriptor of the IP
+// datagram the packet batch is to check ({frame start, 0} for a frame that carries none).
+struct EtherDemuxArgs {
+    const uint8_t*  base;
+    const uint64_t* off;        // frame starts, or nullptr: i * stride
+    const uint16_t* len;        // octets received per frame, or nullptr: len_u
+    uint64_t        stride;
+    uint32_t        len_u;
+    uint32_t        n;
+    uint32_t        eth_cfg;    // NETCSUM_ETHCFG_*
+    uint32_t        have_hw;    // 0: promiscuous
+    uint32_t        hw_lo;      // the interface's address: octets 0-3, little-endian
+    uint32_t        hw_hi;      // octets 4-5
+    uint8_t*        l2_out;     // [n] NETCSUM_L2_*
+    uint64_t*       off_out;    // [n] descriptors for the packet batch
+    uint16_t*       len_out;    // [n]
+};
+constexpr uint32_t kEtherDemuxBlock = 256u;
+inline uint32_t ether_demux_blocks(uint32_t n) { return (n + kEtherDemuxBlock - 1u) / kEtherDemuxBlock; }
+hipError_t launch_ether_demux(const EtherDemuxArgs& a, hipStream_t s);
 void set_last_launch(const char* desc);
 hipError_t launch_hdr_batch(const SegBatchArgs& a, int stages, int h, int grid, hipStream_t s);
 bool stream_supported(const SegBatchArgs& a);  // strided, stride in [len, len+64], len >= 256

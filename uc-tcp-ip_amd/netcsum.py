@@ -55,6 +55,12 @@ RX_DELIVER, RX_DROP_IPV4_CHK_SUM, RX_DROP_TCP_CHK_SUM, RX_DROP_UDP_CHK_SUM = 0, 
 RX_DROP_UDP_NO_CHK_SUM, RX_DROP_ICMPV4_CHK_SUM, RX_DROP_IGMP_CHK_SUM, RX_DROP_ICMPV6_CHK_SUM = 4, 5, 6, 7
 RX_DELIVER_L4_UNVERIFIED, RX_NBR_ACTIONS = 8, 9
 RXCFG_UDP_DISCARD_NO_CHK_SUM = 0x1
+# Layer-2 classes of an Rx burst of Ethernet frames (include/netcsum_mi355x.h (2b''''): the reference's 802.x demux)
+L2_ETHER_IPV4, L2_ETHER_IPV6, L2_SNAP_IPV4, L2_SNAP_IPV6, L2_ETHER_ARP, L2_SNAP_ARP = 0, 1, 2, 3, 4, 5
+L2_INV_FRAME_SIZE, L2_INV_ADDR_DEST, L2_INV_ADDR_SRC, L2_INV_ETHER_TYPE, L2_INV_LEN_FRAME = 6, 7, 8, 9, 10
+L2_INV_LLC_DSAP, L2_INV_LLC_SSAP, L2_INV_LLC_CTRL, L2_INV_SNAP_CODE, L2_INV_SNAP_TYPE = 11, 12, 13, 14, 15
+L2_NBR_CLASSES = 16
+ETHCFG_MCAST_RX = 0x1
 TUNE_GRID_BLOCKS, TUNE_GROUP_LANES, TUNE_NT_LOADS, TUNE_BLOCK_THREADS = 1, 2, 3, 4
 TUNE_KERNEL, TUNE_CHUNKS, TUNE_PROBE, TUNE_GRID_MULT, TUNE_TILE = 5, 6, 7, 8, 9
 TUNE_TX_PASSES = 10
@@ -253,6 +259,14 @@ def lib() -> ctypes.CDLL:
     L.NetUtil_MI355X_FragSumCalc.restype = i32
     L.NetUtil_MI355X_FragSumVerify.argtypes = [vp, u32, vp, u16, ctypes.POINTER(ctypes.c_uint8)]
     L.NetUtil_MI355X_FragSumVerify.restype = i32
+    L.NetUtil_MI355X_RxBurstEther.argtypes = [vp, vp, vp, u64, u16, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.NetUtil_MI355X_RxBurstEther.restype = i32
+    L.NetUtil_MI355X_RxBurstEtherHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, u32, vp, vp, vp, vp, u32]
+    L.NetUtil_MI355X_RxBurstEtherHost.restype = i32
+    L.NetUtil_MI355X_EtherClass.argtypes = [vp, u16, u32, vp, ctypes.POINTER(ctypes.c_uint16)]
+    L.NetUtil_MI355X_EtherClass.restype = ctypes.c_uint8
+    L.NetUtil_MI355X_RxBurstEtherTally.argtypes = [vp, u32, vp]
+    L.NetUtil_MI355X_RxBurstEtherTally.restype = i32
     L.NetUtil_MI355X_RxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, vp, vp, u32]
     L.NetUtil_MI355X_RxBurstHost.restype = i32
     L.NetUtil_MI355X_TxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, vp, u32]
@@ -629,6 +643,69 @@ def frag_sum_verify(frags, pseudo=None):
     return int(out.value), int(err)
 
 
+def _hw_addr(hw_addr):
+    """6 octets (bytes, list, ...) or None -> a ctypes array kept by the caller for the call, or None."""
+    if hw_addr is None:
+        return None
+    b = bytes(hw_addr)
+    if len(b) != 6:
+        raise ValueError("hw_addr: 6 octets")
+    return (ctypes.c_uint8 * 6)(*b)
+
+
+def _frame_bounds(base, off, lens, stride, frame_len, n, flags):
+    """As _pkt_bounds; frames may have lengths without offsets (slots at `stride`)."""
+    if not n:
+        return
+    if off is not None:
+        _require(off, 8 * n, "frame offsets")
+    else:
+        _require(base, (n - 1) * stride + (frame_len if lens is None else 0), "frames")
+    if lens is not None:
+        _require(lens, 2 * n, "frame lengths")
+    if flags is not None:
+        _require(flags, n, "flags")
+
+
+def rx_burst_ether(base, n, action, l2, flags=None, off=None, lens=None, stride=0, frame_len=0, rx_cfg=0, eth_cfg=0,
+                   hw_addr=None, stream=None, check=True):
+    """NetUtil_MI355X_RxBurstEther: an Rx burst of whole Ethernet frames. `l2` receives each frame's L2_*
+    class, `action` / `flags` what rx_burst gives for the IP datagram the frame carries (MALFORMED /
+    DELIVER where it carries none). `lens` (received octets per frame) may come without `off`: slots at
+    `stride`. hw_addr: the interface's 6 octets, or None (promiscuous)."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(l2, n, "layer-2 classes")
+    hw = _hw_addr(hw_addr)
+    err = lib().NetUtil_MI355X_RxBurstEther(_p(base), _p(off), _p(lens), stride, frame_len, n, rx_cfg, eth_cfg, _p(hw),
+                                            _p(action), _p(flags), _p(l2), _stream(stream))
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstEther")
+    return err
+
+
+def ether_class(frame, eth_cfg=0, hw_addr=None, length=None):
+    """NetUtil_MI355X_EtherClass (host logic) of one frame (bytes) -> (L2_* class, header length 14 / 22 / 0).
+    length: the octets received, where they differ from len(frame)."""
+    frame = bytes(frame)
+    hb = HostBytes(frame)
+    hw = _hw_addr(hw_addr)
+    hdr = ctypes.c_uint16(0xFFFF)
+    cls = lib().NetUtil_MI355X_EtherClass(hb.ptr, len(frame) if length is None else length, eth_cfg, _p(hw), ctypes.byref(hdr))
+    return int(cls), int(hdr.value)
+
+
+def rx_burst_ether_tally(l2):
+    """NetUtil_MI355X_RxBurstEtherTally over a host uint8 array -> list of L2_NBR_CLASSES counts."""
+    import numpy as np
+    a = np.ascontiguousarray(l2, dtype=np.uint8)
+    ctr = np.zeros(L2_NBR_CLASSES, np.uint32)
+    _check(lib().NetUtil_MI355X_RxBurstEtherTally(a.ctypes.data if a.size else None, a.size, ctr.ctypes.data),
+           "NetUtil_MI355X_RxBurstEtherTally")
+    return [int(x) for x in ctr]
+
+
 def tx_burst(base, n, flags=None, off=None, lens=None, stride=0, pkt_len=0, stream=None, check=True):
     """NetUtil_MI355X_TxBurst: fill in the checksum fields the stack left to the offload, in place."""
     _pkt_bounds(base, off, lens, stride, pkt_len, n, flags)
@@ -716,6 +793,21 @@ def rx_burst_sums_host(base, n, action, sums, flags=None, off=None, lens=None, s
                                                _p(flags), _p(sums), n_chunks)
     if check:
         _check(err, "NetUtil_MI355X_RxBurstSumsHost")
+    return err
+
+
+def rx_burst_ether_host(base, n, action, l2, flags=None, off=None, lens=None, stride=0, frame_len=0, rx_cfg=0,
+                        eth_cfg=0, hw_addr=None, n_chunks=0, check=True):
+    """NetUtil_MI355X_RxBurstEtherHost: rx_burst_ether over frames and result arrays in host memory."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(l2, n, "layer-2 classes")
+    hw = _hw_addr(hw_addr)
+    err = lib().NetUtil_MI355X_RxBurstEtherHost(_p(base), _p(off), _p(lens), stride, frame_len, n, rx_cfg, eth_cfg, _p(hw),
+                                                _p(action), _p(flags), _p(l2), n_chunks)
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstEtherHost")
     return err
 
 
