@@ -237,3 +237,53 @@ def make_packet_v6(rng: random.Random, kind: str, payload: int | None = None) ->
         k = rng.randint(8, len(b) - 1)                            # addresses are covered too
         b[k] ^= 1 << rng.randint(0, 7)
     return bytes(b)
+
+
+def long_chain_pkts(rng, max_units, n_hdrs=(1,), reps=3):
+    """Valid datagrams whose transport follows Routing / Destination Options chains of n headers of
+    1..max_units 8-B units each (the walk pass finishes whatever the batch kernel's window holds not)."""
+    pkts = []
+    for units in range(1, max_units + 1):
+        for h in n_hdrs:
+            for _ in range(reps):
+                inner = make_packet_v6(rng, rng.choice(["tcp", "udp", "icmp_echo", "icmp_err"]), payload=rng.randint(24, 200))
+                nh, ext = inner[6], b""
+                for _k in range(h):
+                    u = rng.randint(1, units)
+                    t = rng.choice([43, 60])
+                    ext = struct.pack("!BB", nh, u - 1) + ext_body(rng, t, u * 8 - 2) + ext
+                    nh = t
+                body = ext + inner[40:]
+                hdr = inner[:4] + struct.pack("!HB", len(body), nh) + inner[7:40]
+                pkts.append(op.tx_finalize_v6(hdr + body)[0])
+    return pkts
+
+
+LONG_TAILS = ["tcp", "udp", "udp0", "udp_badlen", "tcp_short", "icmp_echo", "icmp_err", "icmp_nd", "icmp_other",
+          "corrupt_l4", "frag", "esp", "hbh_late", "overrun", "trunc"]
+
+
+def long_prefix_pkt(rng, tail, big):
+    """An IPv6 datagram whose chain starts with a Destination Options header of `big` 8-B units (past
+    every batch kernel's window) and ends in `tail`: every transport outcome, Fragment, an opaque
+    header, a late Hop-by-Hop, a header running past the payload, a chain cut at the payload end."""
+    if tail in ("frag", "esp", "hbh_late", "overrun", "trunc"):
+        inner = make_packet_v6(rng, "tcp", payload=rng.randint(0, 200))
+        chain = {"frag": [(60, big), (44, 1)], "esp": [(60, big)], "hbh_late": [(60, big), (0, 1)],
+                 "overrun": [(60, big), (43, 1)], "trunc": [(60, big)]}[tail]
+        final = {"esp": 50, "trunc": 43}.get(tail, 6)
+        nh, ext = _ext_chain(rng, chain, final)
+        body = ext + (b"" if tail == "trunc" else inner[40:])
+    else:
+        inner = make_packet_v6(rng, "tcp" if tail == "corrupt_l4" else tail, payload=rng.randint(0, 300))
+        nh, ext = _ext_chain(rng, [(60, big)] + [(43, 1)] * rng.randint(0, 5), inner[6])
+        body = ext + inner[40:]
+    p = bytearray(inner[:4] + struct.pack("!HB", len(body), nh) + inner[7:40] + body)
+    if tail == "overrun":
+        p[40 + 8 * big + 1] = 255
+    if tail not in ("overrun", "trunc", "frag", "esp", "hbh_late"):
+        p = bytearray(op.tx_finalize_v6(bytes(p), udp_tx_csum=(tail != "udp0"))[0])
+    if tail == "corrupt_l4":
+        k = rng.randint(40 + 8 * big, len(p) - 1)
+        p[k] ^= 1 << rng.randint(0, 7)
+    return bytes(p)

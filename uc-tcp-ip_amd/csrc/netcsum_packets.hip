@@ -1,27 +1,14 @@
-// netcsum_packets.hip — gfx950 IPv4 packet-batch kernels.
+// netcsum_packets.hip — gfx950 IPv4 / IPv6 packet-batch kernels, lane-group form.
 //
-// RX (fused validation, one HBM pass per packet): for every received IPv4 datagram
-//   ip_ok = NetUtil_16BitOnesCplChkSumHdrVerify(ip_hdr, IHL*4)               net_ipv4.c:5247
-//   l4_ok = TCP : DataVerify(seg, {src,dst,0,6,  IP datagram len}, 12)        net_tcp.c:7857
-//           UDP : checksum field 0 -> "no checksum", accepted                 net_udp.c:1916-1920,1971
-//                 else DataVerify(dgram, {src,dst,0,17, UDP len}, 12)         net_udp.c:1934
-//           ICMP: DataVerify(msg, NULL, 0)                                    net_icmpv4.c:1676
-//           IGMP: HdrVerify(msg, msg len)                                     net_igmp.c:1332
-//   with the pseudo-header built in registers from the IP header, instead of two passes
-//   (header verify, then transport verify) over HBM.
-// TX (finalize, in place): the same sums with the checksum fields treated as zero (callers zero
-//   them first, net_ipv4.c:9573), then the checksums are written back:
-//   IP header (offset 10)                 NetUtil_16BitOnesCplChkSumHdrCalc   net_ipv4.c:9578,9586
-//   TCP (hlen+16)                         DataCalc + pseudo-header            net_tcp.c:29824,29862
-//   UDP (hlen+6), 0x0000 -> 0xFFFF        DataCalc + pseudo-header            net_udp.c:2891,2929-2937
-//       (or 0 when UDP Tx checksums are disabled, NET_UDP_CFG_TX_CHK_SUM_EN, net_udp.c:2935)
-//   ICMP / IGMP (hlen+2)                  DataCalc / HdrCalc                  net_icmpv4.c:2204, net_igmp.c:1692
-//
-// Validation order follows the reference: a malformed IPv4 header (version, IHL, total length
-// vs. bytes received; net_ipv4.c:5123-5254) or transport length (net_tcp.c:7808-7818,
-// net_udp.c:1893-1907) means no checksum verdict for that layer. Fragments (MF or offset != 0)
-// get the IP verdict only: their transport checksum covers the reassembled datagram
-// (net_ipv4.c:6523), which a per-packet batch does not have.
+// RX (fused validation, one HBM pass per packet): the IP header's and the transport checksum of every
+//   received datagram are verified with the pseudo-header built in registers from the IP header,
+//   instead of two passes (header verify, then transport verify) over HBM.
+// TX (finalize, in place): the same sums with the checksum fields treated as zero, then the checksums
+//   are written back.
+// Which datagrams get which verdict, where the fields sit, which pseudo-header applies and the order
+// of the checks are the rules of netcsum_ipparse.h (with the reference lines they follow), shared with
+// the run-stream kernels (netcsum_pktstream.hip) and the extension-header walk (netcsum_v6walk.h);
+// this file holds the lane-group window over a packet's first chunks and the sums.
 //
 // Work decomposition: the pipelined v2 structure of netcsum_kernels.hip (G >= 8 lanes per
 // packet, K chunks per lane per pass, the next packet's loads in flight while the current one is
@@ -33,14 +20,12 @@
 #include <stdint.h>
 
 #include "netcsum_device.h"
+#include "netcsum_ipparse.h"
 #include "netcsum_kernels.h"
 
 namespace netcsum {
 
 namespace {
-
-constexpr uint32_t F_IP_OK = 0x01u, F_L4_OK = 0x02u, F_L4_CHECKED = 0x04u, F_UDP_NO_CSUM = 0x08u,
-                   F_MALFORMED = 0x10u, F_FRAGMENT = 0x20u, F_L4_MALFORMED = 0x40u, F_EXT_HDR = 0x80u;
 
 template <int K>
 struct PktStage {
@@ -99,10 +84,6 @@ __device__ __forceinline__ uint32_t pkt_dword(u32x4 v0, uint32_t lead, uint32_t 
     return b ? __builtin_amdgcn_alignbyte(hi, lo, b) : lo;
 }
 
-__device__ __forceinline__ uint32_t be16_at(uint32_t dw, int byte) {   // bytes byte, byte+1 of dw, BE
-    return (((dw >> (8 * byte)) & 0xFFu) << 8) | ((dw >> (8 * byte + 8)) & 0xFFu);
-}
-
 // What frame byte f adds to this lane's unfolded v_sad_u16 accumulator, read from the lane's OWN
 // k = 0 chunk (0 unless the lane holds the byte; weight 2^(8(f&1)) in the absolute LE frame). Tx
 // checksum fields count as zero: their bytes are subtracted where they were summed, with no
@@ -113,248 +94,58 @@ __device__ __forceinline__ uint32_t own_byte(u32x4 v0, uint32_t f, int lane) {
     return ((uint32_t)lane == (f >> 4)) ? (b << (8u * (f & 1u))) : 0u;
 }
 
-struct PktInfo {
-    uint32_t flags;
-    uint32_t hlen;         // IPv4: IP header length. IPv6: bytes before the transport sum's start
-                           // (8: the addresses open the sum; 40: ICMPv6 errors summed without pseudo)
-    uint32_t l4_end;       // packet offset one past the transport part
-    uint32_t l4_csum_off;  // packet offset of the transport checksum field (~0u: none)
-    uint32_t ext_end;      // IPv6: packet offset of the transport header (40 + extension headers)
-    uint32_t pseudo_le;    // little-endian word sum of the pseudo-header (0: none)
-    uint32_t proto;
-    bool     check_l4;
-    // SUMS instantiations (RxBurstSums) only, IPv6 fragments: the payload octets after the Fragment
-    // header (hlen is then the payload's offset), or the walk pass sums it (header past the window)
-    uint32_t frag_len;
-    bool     frag_walk;
+// The group's k = 0 chunks as the rules' accessor (netcsum_ipparse.h): the first 16 G - lead octets of
+// the datagram. The dword reads are cross-lane shuffles, so every lane of the group takes every read.
+template <int G>
+struct GroupWindow {
+    u32x4    v0;
+    uint32_t lead;
+    int      gbase;
+    __device__ __forceinline__ uint32_t limit() const { return 16u * (uint32_t)G - lead; }
+    template <int MinOff>
+    __device__ __forceinline__ uint32_t dword(uint32_t off) const {
+        return pkt_dword(v0, lead, off, gbase);
+    }
 };
 
-__device__ __forceinline__ uint32_t swap16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
+struct PktInfo {
+    ip::Class c;           // what the rules decide (netcsum_ipparse.h)
+    uint32_t hlen;         // IPv4: IP header length. IPv6: bytes before the transport sum's start
+                           // (8: the addresses open the sum; an ICMPv6 error is summed without them: its
+                           // offset; SUMS: a fragment's payload offset). 0: malformed
+    uint32_t l4_end;       // packet offset one past the transport part (0: malformed)
+    uint32_t ext_end;      // IPv6: packet offset of the transport header (40 + extension headers)
+};
 
-// IPv6 (40-B fixed header, RFC 8200): no header checksum; the transport sums take the 40-B
-// pseudo-header {src, dst, upper-layer length (32 bit), 0, next header} of net_ipv6.h:844-852.
-// The addresses are packet bytes [8, 40), contiguous with the transport part, so the transport sum
-// runs over [8, end) and only the length and next-header words are added in registers.
-//   TCP (6)      DataVerify / DataCalc + pseudo                     net_tcp.c:7871-7879, 29839-29850
-//   UDP (17)     as IPv4: 0 = no checksum (Rx), 0 -> 0xFFFF (Tx)    net_udp.c:1947-1957, 2909-2931
-//   ICMPv6 (58)  Rx: types 1, 3, 4 (destination unreachable, time exceeded, parameter problem)
-//                    HdrVerify over the message WITHOUT the pseudo-header  net_icmpv6.c:2910-2920
-//                    types 128-131, 134-137 (echo, MLD, NDP) DataVerify + pseudo  net_icmpv6.c:2923-2942
-//                    other types: rejected before any checksum (INVALID_TYPE)     net_icmpv6.c:2945-2948
-//                Tx: every message through the pseudo-header (DataCalc + pseudo, net_icmpv6.c:1439;
-//                    the error messages' ~HdrCalc(pseudo) field trick, net_icmpv6.c:949-965, gives
-//                    the same value), no 0 -> 0xFFFF substitution
-// Extension headers (net_ipv6.c:8290-8360, RxPktProcessExtHdr): Routing headers (43) the reference
-// accepts (type <= 2 or Segments Left 0, net_ipv6.c:8735-8753) — length (HdrExtLen + 1) * 8,
-// net_ipv6.c:8601 — are skipped, up to 4 of them, while the chain and the transport fields stay
-// inside the bytes the group's first chunks hold (16 * G from the frame start); the transport part
-// then starts after them and the pseudo-header length is the payload length minus their bytes
-// (IP_DatagramLen = IP_TotLen - IPv6_ExtHdrLen, net_ipv6.c:5682). A Fragment header (44) means
-// FRAGMENT: the transport checksum covers the reassembled datagram. Hop-by-Hop / Destination Options
-// headers (whose options must be walked, net_ipv6.c:8604-8672), any other routing header, a chain
-// past that window, and every other extension header (AH, ESP, Mobility, No Next Header,
-// experimental values) get EXT_HDR here; the walk pass (netcsum_v6walk.hip) then judges each of
-// those datagrams by the reference's rules; an extension header running past the payload is
-// MALFORMED.
-__device__ __forceinline__ bool ipv6_ext_hdr(uint32_t nh) {
-    return nh == 0u || nh == 43u || nh == 44u || nh == 50u || nh == 51u || nh == 59u || nh == 60u ||
-           nh == 135u || nh == 139u || nh == 140u || nh == 253u || nh == 254u;
-}
-
+// IPv6: no header checksum. The addresses are packet bytes [8, 40), contiguous with the transport
+// part, so the transport sum runs over [8, end) — less the walked Routing headers [40, ext_end) — and
+// only the length and next-header words of the pseudo-header are added in registers.
 template <int G, bool TX, bool SUMS = false>
-__device__ __forceinline__ PktInfo pkt_parse_v6(u32x4 v0, uint32_t lead, uint32_t avail, int gbase, uint32_t udp_mode,
-                                                uint32_t d0, uint32_t d1) {   // packet dwords 0 and 1
-    PktInfo p{};
-    p.l4_csum_off = ~0u;
-    const uint32_t plen = be16_at(d1, 0);
-    const uint32_t tot = 40u + plen;
-    p.proto = (d1 >> 16) & 0xFFu;
-    p.ext_end = 40u;
-    if (avail < 40u || ((d0 >> 4) & 0xFu) != 6u || tot > avail) {
-        p.flags = F_MALFORMED;
-        p.l4_end = 0u;
-        p.hlen = 0u;
-        return p;
-    }
-    p.l4_end = tot;
-    p.hlen = 8u;
-    // window: transport fields up to off + 24 and the dword reads below stay in the k = 0 chunks
-    constexpr uint32_t kWin = 16u * (uint32_t)G;
-    uint32_t off = 40u;
-    // accepted Routing headers walked here; option headers and rejected-looking Routing headers go
-    // to the walk pass (netcsum_v6walk.hip), which applies NetIPv6_RxOptHdr / RxRoutingHdr's rules
-    for (int e = 0; e < 4 && p.proto == 43u; ++e) {
-        if (lead + off + 8u > kWin) {
-            p.flags |= F_EXT_HDR;
-            return p;
-        }
-        const uint32_t d = pkt_dword(v0, lead, off, gbase);
-        if (((d >> 16) & 0xFFu) > 2u && (d >> 24) != 0u) {
-            p.flags |= F_EXT_HDR;
-            return p;
-        }
-        off += (((d >> 8) & 0xFFu) + 1u) * 8u;
-        p.proto = d & 0xFFu;
-        if (off > tot) {
-            p.flags = F_MALFORMED;
-            p.l4_end = 0u;
-            p.hlen = 0u;
-            return p;
-        }
-    }
-    if (p.proto == 44u) {
-        p.flags |= F_FRAGMENT;
-        if constexpr (SUMS) {
-            if (off + 8u < tot) {                                // octets after the 8-B Fragment header
-                if (lead + off + 8u <= kWin) {
-                    p.hlen = off + 8u;
-                    p.frag_len = tot - (off + 8u);
-                } else {
-                    p.frag_walk = true;
-                }
-            }
-        }
-        return p;
-    }
-    if (ipv6_ext_hdr(p.proto) || (off != 40u && lead + off + 24u > kWin)) {
-        p.flags |= F_EXT_HDR;
-        return p;
-    }
-    p.ext_end = off;
-    const uint32_t ulen = tot - off;                             // upper-layer packet length
-    const uint32_t pseudo = (p.proto << 8) + swap16(ulen);       // length high half is 0 (< 2^16)
-    switch (p.proto) {
-    case 6u:
-        if (ulen < 20u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = off + 16u;
-        p.pseudo_le = pseudo;
-        break;
-    case 17u: {
-        if (ulen < 8u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        const uint32_t du = pkt_dword(v0, lead, off + 4u, gbase);
-        if (be16_at(du, 0) != ulen) {                            // net_udp.c:1903-1907
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = off + 6u;
-        if (!TX && (du >> 16) == 0u) {
-            p.flags |= F_UDP_NO_CSUM | F_L4_OK;
-            return p;
-        }
-        if (TX && !udp_tx_compute(udp_mode, du >> 16)) {
-            p.flags |= F_UDP_NO_CSUM;
-            return p;
-        }
-        p.check_l4 = true;
-        p.pseudo_le = pseudo;
-        break;
-    }
-    case 58u:
-        if (ulen < 4u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = off + 2u;
-        if constexpr (TX) {
-            p.check_l4 = true;
-            p.pseudo_le = pseudo;
-        } else {
-            const uint32_t type = pkt_dword(v0, lead, off, gbase) & 0xFFu;
-            if (type == 1u || type == 3u || type == 4u) {
-                p.check_l4 = true;
-                p.hlen = off;                                    // message alone, no pseudo-header
-            } else if ((type >= 128u && type <= 131u) || (type >= 134u && type <= 137u)) {
-                p.check_l4 = true;
-                p.pseudo_le = pseudo;
-            }
-        }
-        break;
-    default:
-        break;
-    }
+__device__ __forceinline__ PktInfo pkt_parse_v6(const GroupWindow<G>& w, uint32_t avail, uint32_t udp_mode, uint32_t d0,
+                                                uint32_t d1) {                 // packet dwords 0 and 1
+    PktInfo p;
+    p.c = ip::classify6<TX, 0>(w, avail, udp_mode, d0, d1);
+    const ip::Class& c = p.c;
+    p.l4_end = ip::malformed(c) ? 0u : c.tot;
+    p.ext_end = c.l4_off;
+    p.hlen = ip::malformed(c)                     ? 0u
+             : (SUMS && c.frag_len != 0u)         ? c.frag_off
+             : (!TX && c.check_l4 && !c.pseudo)   ? c.l4_off
+                                                  : 8u;
     return p;
 }
 
-template <bool TX>
-__device__ __forceinline__ PktInfo pkt_parse(u32x4 v0, uint32_t lead, uint32_t avail, int gbase, uint32_t udp_mode,
-                                             uint32_t d0, uint32_t d1) {      // packet dwords 0 and 1
-    PktInfo p{};
-    p.l4_csum_off = ~0u;
-    const uint32_t d2 = pkt_dword(v0, lead, 8u, gbase);
-    const uint32_t d3 = pkt_dword(v0, lead, 12u, gbase);
-    const uint32_t d4 = pkt_dword(v0, lead, 16u, gbase);
-    const uint32_t ver = (d0 >> 4) & 0xFu;
-    p.hlen = (d0 & 0xFu) * 4u;
-    const uint32_t tot = be16_at(d0, 2);
-    const uint32_t frag = be16_at(d1, 2) & 0x3FFFu;              // MF | fragment offset
-    p.proto = (d2 >> 8) & 0xFFu;
-    if (avail < 20u || ver != 4u || p.hlen < 20u || tot < p.hlen || tot > avail) {
-        p.flags = F_MALFORMED;
-        p.l4_end = 0u;
-        p.hlen = 0u;
-        return p;
-    }
-    p.l4_end = tot;
-    if (frag != 0u) {
-        p.flags |= F_FRAGMENT;
-        return p;
-    }
-    const uint32_t l4len = tot - p.hlen;
-    const uint32_t src_dst = __builtin_amdgcn_sad_u16(d3, 0u, __builtin_amdgcn_sad_u16(d4, 0u, 0u));
-    switch (p.proto) {
-    case 6u:                                                     // TCP: length = IP datagram length
-        if (l4len < 20u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = p.hlen + 16u;
-        p.pseudo_le = src_dst + (6u << 8) + (((l4len & 0xFFu) << 8) | (l4len >> 8));
-        break;
-    case 17u: {                                                  // UDP
-        if (l4len < 8u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        const uint32_t du = pkt_dword(v0, lead, p.hlen + 4u, gbase);
-        const uint32_t udp_len = be16_at(du, 0);
-        if (udp_len != l4len) {                                  // net_udp.c:1903-1907 (also < 8)
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = p.hlen + 6u;
-        if (!TX && (du >> 16) == 0u) {                           // no checksum transmitted
-            p.flags |= F_UDP_NO_CSUM | F_L4_OK;
-            return p;
-        }
-        if (TX && !udp_tx_compute(udp_mode, du >> 16)) {
-            p.flags |= F_UDP_NO_CSUM;                            // write 0 (NET_UDP_HDR_CHK_SUM_NONE)
-            p.check_l4 = false;
-            return p;
-        }
-        p.check_l4 = true;
-        p.pseudo_le = src_dst + (17u << 8) + (((udp_len & 0xFFu) << 8) | (udp_len >> 8));
-        break;
-    }
-    case 1u:                                                     // ICMPv4, no pseudo-header
-    case 2u:                                                     // IGMP
-        if (l4len < 4u) {
-            p.flags |= F_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = p.hlen + 2u;
-        break;
-    default:
-        break;
-    }
+template <int G, bool TX>
+__device__ __forceinline__ PktInfo pkt_parse(const GroupWindow<G>& w, uint32_t avail, uint32_t udp_mode, uint32_t d0,
+                                             uint32_t d1) {                    // packet dwords 0 and 1
+    PktInfo p;
+    const uint32_t d2 = w.template dword<0>(8u);
+    const uint32_t d3 = w.template dword<0>(12u);
+    const uint32_t d4 = w.template dword<0>(16u);
+    p.c = ip::classify4<TX, 0>(w, avail, udp_mode, d0, d1, d2, d3, d4);
+    p.hlen = p.c.l4_off;
+    p.l4_end = ip::malformed(p.c) ? 0u : p.c.tot;
+    p.ext_end = 40u;
     return p;
 }
 
@@ -398,7 +189,7 @@ template <int G, bool TX, bool BS, bool SUMS = false>
 __device__ __forceinline__ void pkt_store(const PktStore& ps, const PktBatchArgs& A) {
     const uint32_t f = (ps.meta >> 16) & 0xFFu;
     const bool me = (ps.meta >> 26) & 1u;
-    if (me && ((f & F_EXT_HDR) || (SUMS && ps.vals == kFragSumWalk)) && A.defer_word != nullptr) {
+    if (me && ((f & NETCSUM_PKT_EXT_HDR) || (SUMS && ps.vals == kFragSumWalk)) && A.defer_word != nullptr) {
         *A.defer_word = A.defer_tag;                             // the walk pass has work (benign race)
     }
     const bool si = TX && ((ps.meta >> 24) & 1u), sl = TX && ((ps.meta >> 25) & 1u);
@@ -478,16 +269,13 @@ __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const Pkt
     const uint32_t d0 = pkt_dword(st.v[0], lead, 0u, gbase);
     const uint32_t d1 = pkt_dword(st.v[0], lead, 4u, gbase);
     const bool is6 = (VER == 6) || (VER == 0 && ((d0 >> 4) & 0xFu) == 6u);
-    PktInfo p = is6 ? pkt_parse_v6<G, TX, SUMS>(st.v[0], lead, st.avail, gbase, A.udp_tx_csum, d0, d1)
-                   : pkt_parse<TX>(st.v[0], lead, st.avail, gbase, A.udp_tx_csum, d0, d1);
+    const GroupWindow<G> win{st.v[0], lead, gbase};
+    const PktInfo p = is6 ? pkt_parse_v6<G, TX, SUMS>(win, st.avail, A.udp_tx_csum, d0, d1)
+                         : pkt_parse<G, TX>(win, st.avail, A.udp_tx_csum, d0, d1);
+    const ip::Class& pc = p.c;
     // SUMS: a fragment's payload [hlen, l4_end) is summed as a transport part is
-    uint32_t frag_len = 0u;
-    if constexpr (SUMS) {
-        if (p.flags & F_FRAGMENT) {
-            frag_len = is6 ? p.frag_len : p.l4_end - p.hlen;
-        }
-    }
-    const uint32_t end = (p.check_l4 || frag_len != 0u) ? p.l4_end : p.hlen;
+    const uint32_t frag_len = SUMS ? pc.frag_len : 0u;
+    const uint32_t end = (pc.check_l4 || frag_len != 0u) ? p.l4_end : p.hlen;
     const uint32_t rend = lead + end;
     const uint32_t nch = (rend + 15u) >> 4;
     const uint32_t cl = nch - 1u;                                // chunk holding byte rend - 1 (~0u: none)
@@ -535,11 +323,11 @@ __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const Pkt
         acc_l4 -= low_bytes(st.v[0], (int)(lead + p.ext_end) - l16) - low_bytes(st.v[0], (int)(lead + 40u) - l16);
     }
     if (TX) {
-        if (!is6 && !(p.flags & F_MALFORMED)) {
+        if (!is6 && !ip::malformed(pc)) {
             acc_ip -= own_byte(st.v[0], lead + 10u, lane) + own_byte(st.v[0], lead + 11u, lane);
         }
-        if (p.check_l4) {
-            const uint32_t f = lead + p.l4_csum_off;
+        if (pc.check_l4) {
+            const uint32_t f = lead + pc.l4_csum_off;
             acc_l4 -= own_byte(st.v[0], f, lane) + own_byte(st.v[0], f + 1u, lane);
         }
     }
@@ -549,38 +337,16 @@ __device__ __forceinline__ PktStore pkt_consume(const PktStage<K>& st, const Pkt
         sl4 = rot8(sl4);
     }
     sip = fold16(group_sum<G>(sip));
-    sl4 = fold16(group_sum<G>(sl4) + p.pseudo_le);
-    uint32_t f = p.flags;
-    uint32_t cip = ~0u, cl4 = ~0u;                               // Tx values to store; ~0u = none
-    if (!(f & F_MALFORMED)) {
-        if constexpr (!TX) {
-            f |= (is6 || sip == 0xFFFFu) ? F_IP_OK : 0u;          // IPv6: well-formed (no header checksum)
-            if (p.check_l4) {
-                f |= F_L4_CHECKED | ((sl4 == 0xFFFFu) ? F_L4_OK : 0u);
-            }
-        } else {
-            if (!is6) {
-                cip = (~sip) & 0xFFFFu;                          // net_ipv4.c:9578-9586
-            }
-            f |= F_IP_OK;
-            if (p.check_l4) {
-                cl4 = (~sl4) & 0xFFFFu;
-                if (p.proto == 17u && cl4 == 0u) {
-                    cl4 = 0xFFFFu;                               // RFC 768 (net_udp.c:2929-2931)
-                }
-                f |= F_L4_CHECKED | F_L4_OK;
-            } else if ((f & F_UDP_NO_CSUM) && p.l4_csum_off != ~0u) {
-                cl4 = 0u;                                        // no UDP checksum (net_udp.c:2935)
-            }
-        }
-    }
+    sl4 = fold16(group_sum<G>(sl4) + pc.pseudo_le);
+    const ip::Verdict vd = ip::verdict<TX>(pc, sip, sl4);
+    const uint32_t f = vd.flags, cip = vd.cip, cl4 = vd.cl4;     // Tx values to store; ~0u = none
     PktStore ps;
     ps.a = st.a;
     ps.vals = (cip & 0xFFFFu) | ((cl4 & 0xFFFFu) << 16);
     if constexpr (SUMS) {                                        // sl4: the payload's folded sum (no pseudo-header)
-        ps.vals = frag_len != 0u ? (sl4 & 0xFFFFu) | (frag_len << 16) : (p.frag_walk ? kFragSumWalk : 0u);
+        ps.vals = frag_len != 0u ? (sl4 & 0xFFFFu) | (frag_len << 16) : (pc.frag_walk ? kFragSumWalk : 0u);
     }
-    const uint32_t low = TX ? (p.l4_csum_off & 0xFFFFu) : rx_action(f, p.proto, is6, A.rx_cfg);
+    const uint32_t low = TX ? (pc.l4_csum_off & 0xFFFFu) : rx_action(f, pc.proto, is6, A.rx_cfg);
     ps.meta = low | ((f & 0xFFu) << 16) | (cip != ~0u ? 1u << 24 : 0u) |
               (cl4 != ~0u ? 1u << 25 : 0u) | ((valid && lane == 0) ? 1u << 26 : 0u);
     ps.idx = idx;

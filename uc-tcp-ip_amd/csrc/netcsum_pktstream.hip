@@ -1,6 +1,6 @@
 // netcsum_pktstream.hip — gfx950 "run stream" kernel for strided IPv4 packet batches (SURVEY §8(f)
-// rows 1 and 4): fused Rx validation and Tx finalize, the same per-packet semantics as
-// pkt_batch_kernel (netcsum_packets.hip, whose header lists the reference call sites), in the form
+// rows 1 and 4): fused Rx validation and Tx finalize, the per-packet rules of netcsum_ipparse.h
+// (shared with pkt_batch_kernel, netcsum_packets.hip; the reference lines are cited there), in the form
 // of seg_stream_kernel (netcsum_stream.hip): a WAVE owns a run of consecutive packets and reads
 // their bytes exactly once as 1-KiB pieces (every wave-instruction 8 whole aligned lines).
 //
@@ -8,28 +8,26 @@
 //  1. prologue, lane k = packet k of the run: the 96 bytes from the 16-B boundary below the
 //     packet (6 x 16-B loads; the IPv4 header with options <= 60 B plus the transport fields at
 //     <= hlen + 17) are parsed IN THE LANE — version / IHL / total length / fragment / protocol,
-//     UDP length, the pseudo-header {src, dst, 0, proto, len} (net_tcp.c:7851-7857,
-//     net_udp.c:1918-1934) — and the IP header's exact half-word sum [0, hlen) is taken from the
-//     same registers. This overlaps the run's first D pieces in flight.
+//     UDP length, the pseudo-header {src, dst, 0, proto, len} — and the IP header's exact
+//     half-word sum [0, hlen) is taken from the same registers. This overlaps the run's first D
+//     pieces in flight.
 //  2. stream: per packet ONE scalar event at its transport end (`end` = total length, or hlen
 //     when no transport verdict): the exact sum of [start, end) over the wave (prefix masks + DPP
 //     wave_total), parked in lane k of a VGPR. The transport sum is that total minus the IP header
 //     sum — exact integers, so zero iff all its bytes are zero (the reference's 0 / 0xFFFF rule).
-//  3. vector epilogue, lane k = packet k: Tx subtracts the checksum fields (treated as zero,
-//     net_ipv4.c:9573), folds, rotates odd packets, adds the pseudo-header, and derives the same
-//     verdict flags / checksum values as pkt_consume; results are stored once per run: Rx flags as
-//     one coalesced byte store, Tx checksum fields in place (host-order value memcpy'd,
-//     net_ipv4.c:9586, net_tcp.c:29862, net_udp.c:2937).
+//  3. vector epilogue, lane k = packet k: Tx subtracts the checksum fields (treated as zero),
+//     folds, rotates odd packets, adds the pseudo-header, and takes the verdict flags / checksum
+//     values from the shared verdict step; results are stored once per run: Rx flags as one
+//     coalesced byte store, Tx checksum fields in place (the host-order value memcpy'd).
 //
-// IPv6 (VER 6) and mixed rings (VER 0, per datagram by the version nibble) take the same form with
-// the parse of pkt_parse_v6 (netcsum_packets.hip, whose header cites net_ipv6.c / net_icmpv6.c):
+// IPv6 (VER 6) and mixed rings (VER 0, per datagram by the version nibble) take the same form:
 // no header checksum; the transport sum is the stream total minus the window's sum of [0, 8) and of
 // the extension headers [40, transport start) — the addresses [8, 40) stay in, the length and next
 // header words of the 40-B pseudo-header are added in registers; ICMPv6 types 1/3/4 on Rx subtract
-// all of [0, transport start) (no pseudo-header, net_icmpv6.c:2910-2920). Hop-by-Hop / Routing /
-// Destination Options headers are walked inside the lane's window: the first 96 - lead bytes of the
-// datagram (lead = its address mod 16); a chain beyond it gets EXT_HDR, as the lane-group kernel's
-// beyond its 16 G - lead bytes, and the walk pass (netcsum_v6walk.hip) finishes it.
+// all of [0, transport start) (no pseudo-header). Hop-by-Hop / Routing / Destination Options headers
+// are walked inside the lane's window: the first 96 - lead bytes of the datagram (lead = its address
+// mod 16); a chain beyond it gets EXT_HDR, as the lane-group kernel's beyond its 16 G - lead bytes,
+// and the walk pass (netcsum_v6walk.hip) finishes it.
 //
 // Domain (pkt_stream_supported): strided batches (stride >= pkt_len >= 64; gaps <= 64 B for the
 // whole-span bounds 0 and 3, any gap for the live-piece bounds 1 and 2) and offset/length batches
@@ -42,6 +40,7 @@
 
 #include "../../include/netcsum_mi355x.h"
 #include "netcsum_device.h"
+#include "netcsum_ipparse.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
 #include "netcsum_v6walk.h"
@@ -53,10 +52,6 @@ namespace {
 using namespace sv;
 
 constexpr uint32_t kMaxRunPkts = 64u;     // packets per wave run: lane k = packet k
-
-__device__ __forceinline__ uint32_t be16(uint32_t dw, int byte) {   // bytes byte, byte+1 of dw, BE
-    return (((dw >> (8 * byte)) & 0xFFu) << 8) | ((dw >> (8 * byte + 8)) & 0xFFu);
-}
 
 // A window element as an opaque register value. Every select below picks between such values:
 // a select between two LOADS of one array is folded by the optimiser into a load with a computed
@@ -106,31 +101,37 @@ __device__ __forceinline__ uint32_t field_le(uint32_t b0, uint32_t b1, bool odd)
     return odd ? ((b0 << 8) + b1) : (b0 + (b1 << 8));
 }
 
-// SUMS instantiations (RxBurstSums) only: a fragment's payload is streamed too (end = its total
-// length, ip_sum = the bytes before the payload), so the transport slot holds its payload sum. (A base
-// class that is empty otherwise: the other instantiations' packet state keeps its size.)
-template <bool SUMS>
-struct LaneFrag {};
-template <>
-struct LaneFrag<true> {
-    uint32_t frag_len;    // fragment payload octets (0: not a fragment, or nothing to sum)
-    bool     frag_walk;   // IPv6 fragment whose Fragment header ends past the window: the walk sums it
+// The lane's window as the rules' accessor (netcsum_ipparse.h): the first 96 - lead octets of the datagram.
+struct LaneWindow {
+    const u32x4 (&h)[6];
+    uint32_t lead;
+    __device__ __forceinline__ uint32_t limit() const { return 96u - lead; }
+    template <int MinOff>
+    __device__ __forceinline__ uint32_t dword(uint32_t off) const {
+        return pkt_dword_at<MinOff>(h, lead, off);
+    }
 };
 
-template <bool SUMS = false>
-struct LanePktT : LaneFrag<SUMS> {   // lane k's packet after the prologue
-    uint32_t flags;
+// IPv4: the one transport dword the rules or the Tx epilogue need — UDP's length | checksum, else the
+// checksum field — is fetched once, `fd` at offset `fo` (each select chain over the window costs about
+// 40 VALU); a read of any other offset goes to the window.
+struct LaneWindow4 {
+    const u32x4 (&h)[6];
+    uint32_t lead, fo, fd;
+    __device__ __forceinline__ uint32_t limit() const { return 96u - lead; }
+    template <int MinOff>
+    __device__ __forceinline__ uint32_t dword(uint32_t off) const {
+        return off == fo ? fd : pkt_dword_at<MinOff>(h, lead, off);
+    }
+};
+
+struct LanePkt {          // lane k's packet after the prologue
+    ip::Class c;          // what the rules decide (netcsum_ipparse.h)
     uint32_t end;         // packet offset one past the bytes the stream sums (0: none)
     uint32_t ip_sum;      // IPv4: exact half-word sum of the IP header [0, hlen) (absolute LE frame);
                           // IPv6: the bytes of [0, end) outside the transport sum (see the header)
     uint32_t fields;      // Tx: exact contribution of the checksum fields to be zeroed (IP | L4 sum)
     uint32_t l4_field;    // Tx: contribution of the transport field alone
-    uint32_t pseudo_le;
-    uint32_t l4_csum_off; // ~0u: none
-    uint32_t proto;
-    bool     check_l4;
-    bool     malformed;
-    bool     v6;
 };
 
 // Exact half-word sum of packet bytes [0, x) from the lane's window (lead + x <= 96).
@@ -181,246 +182,87 @@ __device__ __forceinline__ uint32_t win_range_sum(const u32x4 (&h)[6], uint32_t 
     return s - low_bytes(h[0], (int)lead);
 }
 
-__device__ __forceinline__ uint32_t swap16(uint32_t x) { return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu); }
-
-// Extension-header values of pkt_parse_v6 (netcsum_packets.hip).
-__device__ __forceinline__ bool ipv6_ext(uint32_t nh) {
-    return nh == 0u || nh == 43u || nh == 44u || nh == 50u || nh == 51u || nh == 59u || nh == 60u ||
-           nh == 135u || nh == 139u || nh == 140u || nh == 253u || nh == 254u;
-}
-
-// IPv6 parse of pkt_parse_v6 from the lane's own window (RFC 8200; net_ipv6.c:8290-8360, 8601,
-// 5682; net_tcp.c:7871-7879; net_udp.c:1947-1957; net_icmpv6.c:2910-2948).
+// IPv6 from the lane's own window: the rules' verdict, then the bytes of [0, end) that are not part of
+// the transport sum. SUMS (RxBurstSums): a fragment's payload is streamed too (end = its total length,
+// ip_sum = the bytes before the payload, which the window holds), so the transport slot holds its sum.
 template <bool TX, bool SUMS = false>
-__device__ __forceinline__ LanePktT<SUMS> lane_parse6(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
-                                               uint32_t avail, bool odd, uint32_t udp_mode, uint32_t d0, uint32_t d1) {
-    LanePktT<SUMS> p{};
-    p.l4_csum_off = ~0u;
-    p.v6 = true;
-    const uint32_t tot = 40u + be16(d1, 0);
-    uint32_t nh = (d1 >> 16) & 0xFFu;
-    if (avail < 40u || ((d0 >> 4) & 0xFu) != 6u || tot > avail) {
-        p.flags = NETCSUM_PKT_MALFORMED;
-        p.malformed = true;
-        return p;
-    }
-    const uint32_t window = 96u - lead;                          // bytes of the datagram in the window
-    uint32_t off = 40u;
-    // Routing headers the reference accepts (type <= 2 or Segments Left 0, net_ipv6.c:8735-8753) are
-    // walked here; Hop-by-Hop / Destination Options headers (whose options NetIPv6_RxOptHdr walks,
-    // net_ipv6.c:8604-8672) and any other routing header go to the walk pass (EXT_HDR), which judges them.
-    for (int e = 0; e < 4 && nh == 43u; ++e) {
-        if (off + 8u > window) {
-            p.flags = NETCSUM_PKT_EXT_HDR;
-            return p;
-        }
-        const uint32_t d = pkt_dword_at<2>(h, lead, off);
-        if (((d >> 16) & 0xFFu) > 2u && (d >> 24) != 0u) {
-            p.flags = NETCSUM_PKT_EXT_HDR;
-            return p;
-        }
-        off += (((d >> 8) & 0xFFu) + 1u) * 8u;
-        nh = d & 0xFFu;
-        if (off > tot) {                                         // extension header past the payload
-            p.flags = NETCSUM_PKT_MALFORMED;
-            p.malformed = true;
-            return p;
+__device__ __forceinline__ LanePkt lane_parse6(const u32x4 (&h)[6], uint32_t lead, uint32_t avail, bool odd,
+                                               uint32_t udp_mode, uint32_t d0, uint32_t d1) {
+    LanePkt p{};
+    p.c = ip::classify6<TX, 2>(LaneWindow{h, lead}, avail, udp_mode, d0, d1);
+    const ip::Class& c = p.c;
+    if constexpr (SUMS) {
+        if (c.frag_len != 0u) {
+            p.end = c.tot;
+            p.ip_sum = win_prefix(h, lead, c.frag_off);
         }
     }
-    if (nh == 44u) {
-        p.flags = NETCSUM_PKT_FRAGMENT;
-        if constexpr (SUMS) {
-            // the payload: the octets after the 8-B Fragment header, [off + 8, tot); the stream total
-            // of [0, tot) less everything before it, which the window holds (else: the walk pass)
-            if (off + 8u < tot) {
-                if (off + 8u <= window) {
-                    p.end = tot;
-                    p.ip_sum = win_prefix(h, lead, off + 8u);
-                    p.frag_len = tot - (off + 8u);
-                } else {
-                    p.frag_walk = true;
-                }
-            }
-        }
-        return p;
-    }
-    if (ipv6_ext(nh) || (off != 40u && off + 24u > window)) {
-        p.flags = NETCSUM_PKT_EXT_HDR;
-        return p;
-    }
-    p.proto = nh;
-    const uint32_t ulen = tot - off;                             // upper-layer length (< 2^16)
-    const uint32_t pseudo = (nh << 8) + swap16(ulen);
-    bool nopseudo = false;
-    switch (nh) {
-    case 6u:
-        if (ulen < 20u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = off + 16u;
-        break;
-    case 17u: {
-        if (ulen < 8u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        const uint32_t du = pkt_dword_at<2>(h, lead, off + 4u);
-        if (be16(du, 0) != ulen) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = off + 6u;
-        if (!TX && (du >> 16) == 0u) {
-            p.flags = NETCSUM_PKT_UDP_NO_CSUM | NETCSUM_PKT_L4_OK;
-            return p;
-        }
-        if (TX && !udp_tx_compute(udp_mode, du >> 16)) {
-            p.flags = NETCSUM_PKT_UDP_NO_CSUM;
-            return p;
-        }
-        p.check_l4 = true;
-        break;
-    }
-    case 58u:
-        if (ulen < 4u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = off + 2u;
-        if constexpr (TX) {
-            p.check_l4 = true;
-        } else {
-            const uint32_t type = pkt_dword_at<2>(h, lead, off) & 0xFFu;
-            if (type == 1u || type == 3u || type == 4u) {
-                p.check_l4 = true;
-                nopseudo = true;                                 // message alone (net_icmpv6.c:2910-2920)
-            } else if ((type >= 128u && type <= 131u) || (type >= 134u && type <= 137u)) {
-                p.check_l4 = true;
-            }
-        }
-        break;
-    default:
-        break;
-    }
-    if (p.check_l4) {
-        p.end = tot;
-        if (off == 40u && !nopseudo) {
+    if (c.check_l4) {
+        p.end = c.tot;
+        if (c.l4_off == 40u && c.pseudo) {
             // the bytes before the addresses: the fixed header's first 8 B, from d0 / d1
             const uint32_t sel = pkt_frame_sel(odd);
             p.ip_sum = frame_sum(d0, sel, frame_sum(d1, sel, 0u));
         } else {                                                 // walked routing headers / ICMPv6 errors
-            const uint32_t s_off = win_prefix(h, lead, off);
-            p.ip_sum = nopseudo ? s_off : s_off - (win_prefix(h, lead, 40u) - win_prefix(h, lead, 8u));
+            const uint32_t s_off = win_prefix(h, lead, c.l4_off);
+            p.ip_sum = !c.pseudo ? s_off : s_off - (win_prefix(h, lead, 40u) - win_prefix(h, lead, 8u));
         }
-        p.pseudo_le = nopseudo ? 0u : pseudo;
         if constexpr (TX) {
-            const uint32_t fd = pkt_dword_at<2>(h, lead, p.l4_csum_off);
+            const uint32_t fd = pkt_dword_at<2>(h, lead, c.l4_csum_off);
             p.l4_field = field_le(fd & 0xFFu, (fd >> 8) & 0xFFu, odd);
         }
     }
     return p;
 }
 
-// IPv4 parse of pkt_parse (netcsum_packets.hip) from the lane's own window; `avail` bytes present.
+// IPv4 from the lane's own window; `avail` bytes present.
 template <bool TX, bool SUMS = false>
-__device__ __forceinline__ LanePktT<SUMS> lane_parse(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
+__device__ __forceinline__ LanePkt lane_parse(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
                                               uint32_t avail, bool odd, uint32_t udp_mode) {
-    LanePktT<SUMS> p{};
-    p.l4_csum_off = ~0u;
+    LanePkt p{};
     const uint32_t d0 = pkt_dword_fixed<0>(wd, lead);
     const uint32_t d1 = pkt_dword_fixed<4>(wd, lead);
     const uint32_t d2 = pkt_dword_fixed<8>(wd, lead);
     const uint32_t d3 = pkt_dword_fixed<12>(wd, lead);
     const uint32_t d4 = pkt_dword_fixed<16>(wd, lead);
-    const uint32_t ver = (d0 >> 4) & 0xFu;
-    uint32_t hlen = (d0 & 0xFu) * 4u;
-    const uint32_t tot = be16(d0, 2);
-    const uint32_t frag = be16(d1, 2) & 0x3FFFu;                 // MF | fragment offset
-    p.proto = (d2 >> 8) & 0xFFu;
-    if (avail < 20u || ver != 4u || hlen < 20u || tot < hlen || tot > avail) {
-        p.flags = NETCSUM_PKT_MALFORMED;
-        p.malformed = true;
+    p.c = ip::classify4<TX, 1, LaneWindow, false>(LaneWindow{h, lead}, avail, udp_mode, d0, d1, d2, d3, d4);
+    ip::Class& c = p.c;                                          // the header step; the transport step below
+    // decided by the header step: malformed (no transport offset) or a fragment (its payload offset).
+    // (The same as c.flags != 0; tested this way the dense IPv4 kernels keep the 7 waves per SIMD they
+    // had, and were measured at, before the rules moved out: profiles/ipparse_refactor_resources.txt.)
+    const bool decided = c.l4_off == 0u || c.frag_off != 0u;
+    if (ip::malformed(c)) {
         return p;                                                // end 0: nothing summed
     }
     // exact sum of the IP header [0, hlen): the 20-B base header from d0..d4; with options, from the
     // window (lead + hlen <= 75 < 96)
+    const uint32_t hlen = c.l4_off;
     if (hlen == 20u) {
         const uint32_t sel = pkt_frame_sel(odd);
         p.ip_sum = frame_sum(d0, sel, frame_sum(d1, sel, frame_sum(d2, sel, frame_sum(d3, sel, frame_sum(d4, sel, 0u)))));
     } else {
         uint32_t s = 0u - low_bytes(h[0], (int)lead);
 #pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            s += low_bytes(h[c], min(max((int)(lead + hlen) - 16 * c, 0), 16));
+        for (int k = 0; k < 5; ++k) {
+            s += low_bytes(h[k], min(max((int)(lead + hlen) - 16 * k, 0), 16));
         }
         p.ip_sum = s;
     }
     p.fields = TX ? field_le((d2 >> 16) & 0xFFu, d2 >> 24, odd) : 0u;   // IP checksum field, offset 10
     p.end = hlen;
-    if (frag != 0u) {
-        p.flags = NETCSUM_PKT_FRAGMENT;
-        if constexpr (SUMS) {                                    // the payload [hlen, tot) is streamed too
-            p.end = tot;
-            p.frag_len = tot - hlen;
+    if (decided) {                                               // FRAGMENT
+        if (SUMS && c.frag_len != 0u) {
+            p.end = c.tot;                                       // the payload [hlen, tot) is streamed too
         }
         return p;
     }
-    const uint32_t l4len = tot - hlen;
-    const uint32_t src_dst = __builtin_amdgcn_sad_u16(d3, 0u, __builtin_amdgcn_sad_u16(d4, 0u, 0u));
-    const uint32_t fo = p.proto == 17u ? hlen + 4u : (p.proto == 6u ? hlen + 16u : hlen + 2u);
-    const uint32_t fd = pkt_dword_at<1>(h, lead, fo);              // UDP: len | csum; TCP / ICMP / IGMP: csum
-    switch (p.proto) {
-    case 6u:
-        if (l4len < 20u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = hlen + 16u;
-        p.pseudo_le = src_dst + (6u << 8) + (((l4len & 0xFFu) << 8) | (l4len >> 8));
-        p.l4_field = TX ? field_le(fd & 0xFFu, (fd >> 8) & 0xFFu, odd) : 0u;
-        break;
-    case 17u: {
-        if (l4len < 8u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        const uint32_t udp_len = be16(fd, 0);
-        if (udp_len != l4len) {                                  // net_udp.c:1903-1907
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.l4_csum_off = hlen + 6u;
-        if (!TX && (fd >> 16) == 0u) {                           // no checksum transmitted
-            p.flags = NETCSUM_PKT_UDP_NO_CSUM | NETCSUM_PKT_L4_OK;
-            return p;
-        }
-        if (TX && !udp_tx_compute(udp_mode, fd >> 16)) {
-            p.flags = NETCSUM_PKT_UDP_NO_CSUM;                   // write 0 (NET_UDP_HDR_CHK_SUM_NONE)
-            return p;
-        }
-        p.check_l4 = true;
-        p.pseudo_le = src_dst + (17u << 8) + (((udp_len & 0xFFu) << 8) | (udp_len >> 8));
-        p.l4_field = TX ? field_le((fd >> 16) & 0xFFu, fd >> 24, odd) : 0u;
-        break;
-    }
-    case 1u:                                                     // ICMPv4 / IGMP: no pseudo-header
-    case 2u:
-        if (l4len < 4u) {
-            p.flags = NETCSUM_PKT_L4_MALFORMED;
-            return p;
-        }
-        p.check_l4 = true;
-        p.l4_csum_off = hlen + 2u;
-        p.l4_field = TX ? field_le(fd & 0xFFu, (fd >> 8) & 0xFFu, odd) : 0u;
-        break;
-    default:
-        break;
-    }
-    if (p.check_l4) {
-        p.end = tot;
+    const uint32_t fo = c.proto == 17u ? hlen + 4u : (c.proto == 6u ? hlen + 16u : hlen + 2u);
+    const uint32_t fd = pkt_dword_at<1>(h, lead, fo);            // UDP: len | csum; TCP / ICMP / IGMP: csum
+    ip::transport<TX, false, 1>(LaneWindow4{h, lead, fo, fd}, udp_mode, ip::addr4_le(d3, d4), c);
+    if (c.check_l4) {
+        p.end = c.tot;
+        const uint32_t f16 = c.proto == 17u ? fd >> 16 : fd;
+        p.l4_field = TX ? field_le(f16 & 0xFFu, (f16 >> 8) & 0xFFu, odd) : 0u;
     }
     return p;
 }
@@ -434,7 +276,7 @@ __device__ __forceinline__ void store_field(uint8_t* p, uint32_t v) {    // memc
 // REC (Tx only): instead of writing the checksum fields, write one PktTxRecord per packet (dense,
 // coalesced); pkt_scatter_kernel then writes the fields in a pass of its own.
 template <int VER, bool TX, bool SUMS = false>
-__device__ __forceinline__ LanePktT<SUMS> lane_parse_ver(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
+__device__ __forceinline__ LanePkt lane_parse_ver(const uint32_t (&wd)[24], const u32x4 (&h)[6], uint32_t lead,
                                                   uint32_t avail, bool odd, uint32_t udp_mode) {
     if constexpr (VER == 4) {
         return lane_parse<TX, SUMS>(wd, h, lead, avail, odd, udp_mode);
@@ -442,7 +284,7 @@ __device__ __forceinline__ LanePktT<SUMS> lane_parse_ver(const uint32_t (&wd)[24
         const uint32_t d0 = pkt_dword_fixed<0>(wd, lead);
         const uint32_t d1 = pkt_dword_fixed<4>(wd, lead);
         if (VER == 6 || ((d0 >> 4) & 0xFu) == 6u) {
-            return lane_parse6<TX, SUMS>(wd, h, lead, avail, odd, udp_mode, d0, d1);
+            return lane_parse6<TX, SUMS>(h, lead, avail, odd, udp_mode, d0, d1);
         }
         return lane_parse<TX, SUMS>(wd, h, lead, avail, odd, udp_mode);
     }
@@ -544,7 +386,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
         wd[4 * c + 3] = h[c].w;
     }
     const bool odd = (prel & 1u) != 0u;                        // O is 128-B aligned
-    const LanePktT<SUMS> pk = lane_parse_ver<VER, TX, SUMS>(wd, h, plead, avail, odd, A.udp_tx_csum);
+    const LanePkt pk = lane_parse_ver<VER, TX, SUMS>(wd, h, plead, avail, odd, A.udp_tx_csum);
     const uint32_t end_v = mine ? pk.end : 0u;
     // Live forms: datagrams whose summed bytes lie inside the lane's window (40-B ACKs; nothing to
     // sum) are summed here from the window: the stream neither marks their sectors nor walks their
@@ -712,11 +554,12 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
     const bool walk_here = kWalkHere && A.defer_word == nullptr;           // wave-uniform
     bool need = false;
     if (mine) {
-    // vector epilogue: lane k = packet s_begin + k (pkt_consume's verdicts / values)
+    // vector epilogue: lane k = packet s_begin + k
+    const ip::Class& pc = pk.c;
     uint32_t acc_ip = pk.ip_sum, acc_l4 = tot_v - pk.ip_sum;
-    if (TX && !pk.malformed) {
+    if (TX && !ip::malformed(pc)) {
         acc_ip -= pk.fields;
-        if (pk.check_l4) {
+        if (pc.check_l4) {
             acc_l4 -= pk.l4_field;
         }
     }
@@ -725,33 +568,13 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
         sip = rot8(sip);
         sl4 = rot8(sl4);
     }
-    sl4 = fold16(sl4 + pk.pseudo_le);
-    uint32_t f = pk.flags;
-    uint32_t cip = ~0u, cl4 = ~0u;
-    if (!pk.malformed) {
-        if constexpr (!TX) {
-            f |= (pk.v6 || sip == 0xFFFFu) ? NETCSUM_PKT_IP_OK : 0u;   // IPv6: well-formed (no header checksum)
-            if (pk.check_l4) {
-                f |= NETCSUM_PKT_L4_CHECKED | ((sl4 == 0xFFFFu) ? NETCSUM_PKT_L4_OK : 0u);
-            }
-        } else {
-            cip = pk.v6 ? ~0u : ((~sip) & 0xFFFFu);             // net_ipv4.c:9578-9586; IPv6: none
-            f |= NETCSUM_PKT_IP_OK;
-            if (pk.check_l4) {
-                cl4 = (~sl4) & 0xFFFFu;
-                if (pk.proto == 17u && cl4 == 0u) {
-                    cl4 = 0xFFFFu;                               // RFC 768 (net_udp.c:2929-2931)
-                }
-                f |= NETCSUM_PKT_L4_CHECKED | NETCSUM_PKT_L4_OK;
-            } else if ((f & NETCSUM_PKT_UDP_NO_CSUM) && pk.l4_csum_off != ~0u) {
-                cl4 = 0u;                                        // no UDP checksum (net_udp.c:2935)
-            }
-        }
-    }
+    sl4 = fold16(sl4 + pc.pseudo_le);
+    const ip::Verdict vd = ip::verdict<TX>(pc, sip, sl4);
+    const uint32_t f = vd.flags, cip = vd.cip, cl4 = vd.cl4;
     const uint32_t idx = s_begin + lane;
     need = walk_here && (f & NETCSUM_PKT_EXT_HDR) != 0u;               // walk_one writes its verdict
     if constexpr (SUMS) {
-        need = need || (walk_here && pk.frag_walk);
+        need = need || (walk_here && pc.frag_walk);
     }
     if (A.defer_word != nullptr && (f & NETCSUM_PKT_EXT_HDR)) {
         *A.defer_word = A.defer_tag;                             // the walk pass has work (benign race)
@@ -760,7 +583,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
         // one 8-B store per packet (a struct assignment compiles to four partial stores, which
         // made this pass ~70 us slower on 1 M packets)
         const uint64_t r = (uint64_t)((cip & 0xFFFFu) | ((cl4 & 0xFFFFu) << 16)) |
-                           ((uint64_t)(pk.l4_csum_off & 0xFFFFu) << 32) | ((uint64_t)(f & 0xFFu) << 48) |
+                           ((uint64_t)(pc.l4_csum_off & 0xFFFFu) << 32) | ((uint64_t)(f & 0xFFu) << 48) |
                            ((uint64_t)((cip != ~0u ? 1u : 0u) | (cl4 != ~0u ? 2u : 0u)) << 56);
         reinterpret_cast<uint64_t*>(rec)[idx] = r;
     } else {
@@ -768,12 +591,12 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
         A.flags_out[idx] = (uint8_t)f;
     }
     if (!TX && A.action_out && !need) {
-        A.action_out[idx] = (uint8_t)rx_action(f, pk.proto, pk.v6, A.rx_cfg);
+        A.action_out[idx] = (uint8_t)rx_action(f, pc.proto, pc.v6, A.rx_cfg);
     }
     if constexpr (SUMS) {
         // the run's records, one coalesced dword store: sl4 is the payload's folded sum (no pseudo-header)
         if (!need) {
-            A.sums_out[idx] = pk.frag_len != 0u ? (sl4 & 0xFFFFu) | (pk.frag_len << 16) : 0u;
+            A.sums_out[idx] = pc.frag_len != 0u ? (sl4 & 0xFFFFu) | (pc.frag_len << 16) : 0u;
         }
     }
     if constexpr (TX) {
@@ -782,10 +605,10 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
             store_field(p + 10, cip);
         }
         if (cl4 != ~0u) {
-            store_field(p + pk.l4_csum_off, cl4);
+            store_field(p + pc.l4_csum_off, cl4);
         }
         if (A.fieldpos_out && !need) {
-            A.fieldpos_out[idx] = (cip != ~0u ? kFieldIP : 0u) | (cl4 != ~0u ? kFieldL4 | (pk.l4_csum_off & 0xFFFFu) : 0u);
+            A.fieldpos_out[idx] = (cip != ~0u ? kFieldIP : 0u) | (cl4 != ~0u ? kFieldL4 | (pc.l4_csum_off & 0xFFFFu) : 0u);
         }
     }
     }

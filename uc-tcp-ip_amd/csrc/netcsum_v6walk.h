@@ -1,29 +1,36 @@
 // netcsum_v6walk.h — the IPv6 extension-header walk of one datagram by a 16-lane group (walk_one),
 // shared by the walk pass (netcsum_v6walk.hip, after the Tx and lane-group batch kernels) and by the
 // run-stream Rx kernel (netcsum_pktstream.hip), which finishes its own deferred datagrams at the end
-// of each run. See netcsum_v6walk.hip for the rules and the reference lines they follow.
+// of each run. The chain's rules are here (netcsum_v6walk.hip describes the pass); the transport and
+// verdict rules after the chain are netcsum_ipparse.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "netcsum_device.h"
+#include "netcsum_ipparse.h"
 #include "netcsum_kernels.h"
 
 namespace netcsum {
 namespace v6walk {
 
-constexpr uint32_t W_IP_OK = 0x01u, W_L4_OK = 0x02u, W_L4_CHECKED = 0x04u, W_UDP_NO_CSUM = 0x08u,
-                   W_MALFORMED = 0x10u, W_FRAGMENT = 0x20u, W_L4_MALFORMED = 0x40u, W_EXT_HDR = 0x80u;
-
-__device__ __forceinline__ bool ext_hdr_value(uint32_t nh) {   // net_ipv6.h NET_IP_HDR_PROTOCOL_EXT_*
-    return nh == 0u || nh == 43u || nh == 44u || nh == 50u || nh == 51u || nh == 59u || nh == 60u ||
-           nh == 135u || nh == 139u || nh == 140u || nh == 253u || nh == 254u;
-}
-
-__device__ __forceinline__ uint32_t be16(const uint8_t* p, uint32_t k) {
-    return ((uint32_t)p[k] << 8) | (uint32_t)p[k + 1u];
-}
+// The datagram's octets as the rules' accessor (netcsum_ipparse.h): every octet is one load away, so
+// the window is the whole datagram; octets at or past its end read as 0.
+struct ByteWindow {
+    const uint8_t* p;
+    uint32_t       tot;
+    __device__ __forceinline__ uint32_t limit() const { return tot; }
+    template <int MinOff>
+    __device__ __forceinline__ uint32_t dword(uint32_t off) const {
+        uint32_t d = 0u;
+#pragma unroll
+        for (uint32_t k = 0u; k < 4u; ++k) {
+            d |= (off + k < tot ? (uint32_t)p[off + k] : 0u) << (8u * k);
+        }
+        return d;
+    }
+};
 
 // NetIPv6_RxOptHdr's option walk (net_ipv6.c:8604-8672) over a Hop-by-Hop / Destination Options
 // header h of eh_len octets: an option whose type & 0x1F is not Pad1 (0), PadN (1) or Router Alert
@@ -95,107 +102,69 @@ __device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint
     if (avail < 40u || (p[0] >> 4) != 6u) {
         return;                                     // not IPv6: the batch kernel's flag stands
     }
-    const uint32_t tot = 40u + be16(p, 4u);
+    const uint32_t tot = 40u + (((uint32_t)p[4] << 8) | (uint32_t)p[5]);
     if (tot > avail) {
         return;                                     // MALFORMED already (never EXT_HDR)
     }
-    uint32_t nh = p[6], off = 40u, f = 0u;
+    ip::Class c{};                                  // (flags: what this walk alone decides)
+    c.v6 = true;
+    c.tot = tot;
+    c.l4_csum_off = ~0u;
+    uint32_t nh = p[6], off = 40u;
     while (nh == 0u || nh == 43u || nh == 60u) {   // off grows by >= 8 per header: ends by tot
         if (nh == 0u && off != 40u) {
-            f = W_IP_OK | W_EXT_HDR;                // Hop-by-Hop only first (net_ipv6.c:8307)
+            c.flags = NETCSUM_PKT_EXT_HDR;          // Hop-by-Hop only first (net_ipv6.c:8307)
             break;
         }
         if (off + 8u > tot) {
-            f = W_MALFORMED;                        // the header would run past the payload
+            c.flags = NETCSUM_PKT_MALFORMED;        // the header would run past the payload
             break;
         }
         const uint32_t eh_len = ((uint32_t)p[off + 1u] + 1u) * 8u;
         if (off + eh_len > tot) {
-            f = W_MALFORMED;                        // (the reference reads on past the payload)
+            c.flags = NETCSUM_PKT_MALFORMED;        // (the reference reads on past the payload)
             break;
         }
         if (!(nh == 43u ? routing_accepts(p + off) : options_accept(p + off, eh_len))) {
-            f = W_IP_OK | W_EXT_HDR;                // the reference drops the datagram here
+            c.flags = NETCSUM_PKT_EXT_HDR;          // the reference drops the datagram here
             break;
         }
         nh = p[off];
         off += eh_len;
     }
-    uint32_t csum_off = ~0u;
+    c.proto = nh;
+    c.l4_off = off;
     uint32_t frag_rec = 0u;                         // SUMS: sum | len << 16
-    bool pseudo = false, check = false;
-    if (f == 0u) {
-        f = W_IP_OK;
-        const uint32_t ulen = tot - off;
+    if (c.flags == 0u) {
         if (nh == 44u) {
-            f |= W_FRAGMENT;
+            c.flags = NETCSUM_PKT_FRAGMENT;
             if constexpr (SUMS) {
-                if (ulen > 8u) {                    // octets after the 8-B Fragment header
+                if (tot - off > 8u) {               // octets after the 8-B Fragment header
                     // group_sum folds big-endian half-words; the record holds the host-order value
-                    frag_rec = rot8(group_sum(p, off + 8u, tot, ~0u, lane)) | ((ulen - 8u) << 16);
+                    frag_rec = rot8(group_sum(p, off + 8u, tot, ~0u, lane)) | ((tot - off - 8u) << 16);
                 }
             }
-        } else if (ext_hdr_value(nh)) {
-            f |= W_EXT_HDR;
-        } else if (nh == 6u) {
-            if (ulen < 20u) {
-                f |= W_L4_MALFORMED;
-            } else {
-                csum_off = off + 16u;
-                pseudo = check = true;
-            }
-        } else if (nh == 17u) {
-            if (ulen < 8u || be16(p, off + 4u) != ulen) {
-                f |= W_L4_MALFORMED;
-            } else {
-                csum_off = off + 6u;
-                if (!TX && be16(p, off + 6u) == 0u) {
-                    f |= W_UDP_NO_CSUM | W_L4_OK;
-                } else if (TX && !udp_tx_compute(A.udp_tx_csum, be16(p, off + 6u))) {
-                    f |= W_UDP_NO_CSUM;
-                    if (lane == 0u) {
-                        p[csum_off] = 0u;           // NET_UDP_HDR_CHK_SUM_NONE (net_udp.c:2935)
-                        p[csum_off + 1u] = 0u;
-                        if (A.fieldpos_out) A.fieldpos_out[i] = kFieldL4 | csum_off;
-                    }
-                } else {
-                    pseudo = check = true;
-                }
-            }
-        } else if (nh == 58u) {
-            if (ulen < 4u) {
-                f |= W_L4_MALFORMED;
-            } else {
-                csum_off = off + 2u;
-                const uint32_t type = p[off];
-                if (TX || (type >= 128u && type <= 131u) || (type >= 134u && type <= 137u)) {
-                    pseudo = check = true;
-                } else if (type == 1u || type == 3u || type == 4u) {
-                    check = true;                   // HdrVerify over the message alone
-                }
-            }
+        } else if (ip::ext_hdr_value(nh)) {
+            c.flags = NETCSUM_PKT_EXT_HDR;
+        } else {
+            ip::transport<TX, true, 0>(ByteWindow{p, tot}, A.udp_tx_csum, 0u, c);
         }
     }
-    if (check) {
-        uint32_t s = group_sum(p, off, tot, TX ? csum_off : ~0u, lane);
-        if (pseudo) {
-            s += group_sum(p, 8u, 40u, ~0u, lane) + (tot - off) + nh;   // addresses, length, next header
-        }                                           // (folded values: no overflow)
-        const uint32_t r = fold16(s);
-        if constexpr (TX) {
-            uint32_t c = (~r) & 0xFFFFu;
-            if (nh == 17u && c == 0u) {
-                c = 0xFFFFu;                        // RFC 768 (net_udp.c:2929-2931)
-            }
-            if (lane == 0u) {
-                p[csum_off] = (uint8_t)(c >> 8);
-                p[csum_off + 1u] = (uint8_t)c;
-                if (A.fieldpos_out) A.fieldpos_out[i] = kFieldL4 | csum_off;
-            }
-            f |= W_L4_CHECKED | W_L4_OK;
-        } else {
-            f |= W_L4_CHECKED | (r == 0xFFFFu ? W_L4_OK : 0u);
+    uint32_t sl4 = 0u;
+    if (c.check_l4) {
+        uint32_t s = group_sum(p, off, tot, TX ? c.l4_csum_off : ~0u, lane);
+        if (c.pseudo) {
+            s += group_sum(p, 8u, 40u, ~0u, lane);  // the addresses (folded values: no overflow)
         }
+        // group_sum folds big-endian half-words; the rules take the host-order (little-endian) sum
+        sl4 = fold16(rot8(fold16(s)) + c.pseudo_le);
+    }
+    const ip::Verdict vd = ip::verdict<TX>(c, 0u, sl4);
+    const uint32_t f = vd.flags;
+    if (TX && vd.cl4 != ~0u && lane == 0u) {        // memcpy of the host-order value
+        p[c.l4_csum_off] = (uint8_t)(vd.cl4 & 0xFFu);
+        p[c.l4_csum_off + 1u] = (uint8_t)(vd.cl4 >> 8);
+        if (A.fieldpos_out) A.fieldpos_out[i] = kFieldL4 | c.l4_csum_off;
     }
     if (lane == 0u) {
         if (A.flags_out) A.flags_out[i] = (uint8_t)f;

@@ -15,17 +15,14 @@
 //
 // Datagrams are rare on this path (option headers, chains of more than 4 routing headers or longer
 // than ~50 bytes), and the pass is launched only when the batch kernels deferred one (their
-// deferral word, launch_pkt_v6_walk). The verdict rules are pkt_parse_v6's (netcsum_packets.hip; the same reference lines):
-//   TCP (6)     DataVerify / DataCalc + pseudo {src, dst, ulen, 0, 6}        net_tcp.c:7871-7879, 29839-29862
-//   UDP (17)    length check, field 0 = no checksum (Rx), 0 -> 0xFFFF (Tx)   net_udp.c:1903-1957, 2909-2937
-//   ICMPv6 (58) Rx types 1, 3, 4 without the pseudo-header, 128-131 / 134-137 with it, others no verdict;
-//               Tx every type with it                                         net_icmpv6.c:2910-2948, 1439
-// with ulen = payload length - extension-header bytes (net_ipv6.c:5682); Fragment (44) -> FRAGMENT,
-// another extension header, a late Hop-by-Hop, an option with a discard action or a routing type > 2
-// with Segments Left != 0 -> EXT_HDR (no transport verdict: the reference drops those,
-// net_ipv6.c:8307-8309, 8465-8476, 8630-8671, 8735-8753), a header running past the payload ->
-// MALFORMED. The batch kernels leave every datagram with a Hop-by-Hop or Destination Options header
-// to this pass (its options must be walked).
+// deferral word, launch_pkt_v6_walk). Once the chain is walked, the transport and verdict rules are
+// the ones every packet kernel uses (netcsum_ipparse.h, which cites the reference), with the
+// upper-layer length = payload length - extension-header bytes. The chain's own rules live here
+// (netcsum_v6walk.h): Fragment (44) -> FRAGMENT; another extension header, a late Hop-by-Hop, an
+// option with a discard action or a routing type > 2 with Segments Left != 0 -> EXT_HDR (no transport
+// verdict: the reference drops those, net_ipv6.c:8307-8309, 8465-8476, 8630-8671, 8735-8753); a header
+// running past the payload -> MALFORMED. The batch kernels leave every datagram with a Hop-by-Hop or
+// Destination Options header to this pass (its options must be walked).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -52,7 +49,7 @@ __global__ void __launch_bounds__(256) pkt_v6_walk_kernel(PktBatchArgs A) {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint64_t w0 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); w0 < A.n; w0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t i = w0 + lane;
-        bool need = i < A.n && (A.flags_out[i] & v6walk::W_EXT_HDR) != 0u;
+        bool need = i < A.n && (A.flags_out[i] & NETCSUM_PKT_EXT_HDR) != 0u;
         if constexpr (SUMS) {
             need = need || (i < A.n && A.sums_out[i] == kFragSumWalk);
         }
