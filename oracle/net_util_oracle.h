@@ -7,10 +7,11 @@
  * written from the reference's algorithm, not copied from it. Each function cites the
  * reference lines it restates.
  *
- * PARITY STATUS: "parity unpinned by the reference's own artefacts". The reference ships no
- * tests, fixtures or golden vectors, and its net_util.c cannot be built in this image
- * without writing stand-ins for the un-vendored Micrium uC-CPU / uC-LIB / KAL headers, which this
- * project does not do. The oracle is pinned instead by
+ * PARITY STATUS: pinned to output of the reference's own net_util.c. The reference ships no tests,
+ * fixtures or golden vectors; oracle/ref/ holds stand-ins for the un-vendored Micrium
+ * uC-CPU / uC-LIB / KAL headers with which `make ref` builds the untouched net_util.c where a
+ * reference tree is present, and tests/golden/reference_vectors.json records what it returns
+ * (tests/test_reference_cpu.py). The oracle is pinned besides by
  *   - the two published external known-answer tests (RFC 1071 §3 worked example; the classic
  *     IPv4 header 4500 0073 … → b861), tests/test_oracle_kat.py;
  *   - an independent second restatement written from RFC 1071 + SURVEY Appendix B in numpy

@@ -4,8 +4,8 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 only as the checker / CPU baseline. The product library never links or calls it.
 
 The C restatement it loads is documented in oracle/net_util_oracle.h (parity status: pinned by
-external RFC 1071 / IPv4 KATs and by the independent numpy restatement oracle/oracle_np.py;
-"parity unpinned" by the reference's own artefacts, which do not exist).
+external RFC 1071 / IPv4 KATs, by the independent numpy restatement oracle/oracle_np.py, and by
+tests/golden/reference_vectors.json, recorded from the reference's own net_util.c: oracle/ref/).
 """
 from __future__ import annotations
 

@@ -1,0 +1,22 @@
+/* Stand-in for the CPU core services header (see cpu.h here). The stack asks for a core version
+ * of at least 1.30 and, with 32-bit timestamps disabled, uses only the type names below. */
+#ifndef NETCSUM_REF_CPU_CORE_H
+#define NETCSUM_REF_CPU_CORE_H
+
+#include <cpu.h>
+#include <lib_def.h>
+
+#define CPU_CORE_VERSION     13000u
+
+typedef int         CPU_ERR;
+#define CPU_ERR_NONE         0
+
+typedef CPU_INT32U  CPU_TS32;
+typedef CPU_INT64U  CPU_TS64;
+typedef CPU_TS32    CPU_TS;
+typedef CPU_INT32U  CPU_TS_TMR_FREQ;
+
+#define CPU_CFG_TS_32_EN     DEF_DISABLED
+#define CPU_CFG_TS_64_EN     DEF_DISABLED
+
+#endif

@@ -2,10 +2,12 @@
 """Generate tests/golden/netutil_golden.json — small committed input/expected-output vectors for
 the four reference functions (Source/net_util.c:159, :245, :344, :428).
 
-Where the expected values come from: the reference ships no fixtures and its net_util.c cannot be
-built in this image without stand-in platform headers, so the expected values
-are produced by the C oracle (oracle/net_util_oracle.c) and, at generation time, asserted equal to
-the independent numpy oracle (oracle/oracle_np.py). Two external KATs (RFC 1071 §3, IPv4 header)
+Where the expected values come from: the reference ships no fixtures, and this file predates the
+recipe that builds its net_util.c (oracle/ref/), so the expected values here are
+produced by the C oracle (oracle/net_util_oracle.c) and, at generation time, asserted equal to
+the independent numpy oracle (oracle/oracle_np.py). tests/test_reference_cpu.py compares every case
+of the file with the live reference where that is built; vectors recorded from the reference itself
+are in reference_vectors.json (make_reference_vectors.py). Two external KATs (RFC 1071 §3, IPv4 header)
 are included with their PUBLISHED answers, not computed ones. The vectors thereby pin every later
 change of either oracle or of the GPU path to today's KAT-pinned behaviour.
 
