@@ -25,7 +25,7 @@ KERNEL_FILES = {"seg_stream": "netcsum_stream.hip", "seg_live": "netcsum_stream.
                 "seg_hdrstream": "netcsum_hdrstream.hip", "seg_hdr_": "netcsum_hdr.hip", "pkt_stream": "netcsum_pktstream.hip",
                 "pkt_scatter": "netcsum_pktstream.hip", "pkt_batch": "netcsum_packets.hip", "pkt_v6_walk": "netcsum_v6walk.hip",
                 "chain_": "netcsum_chains.hip", "crc_": "netcsum_crc.hip", "seg_small": "netcsum_small.hip"}
-COMMON = ["netcsum_device.h", "netcsum_kernels.h", "netcsum_stream.h"]
+COMMON = ["netcsum_device.h", "netcsum_kernels.h", "netcsum_stream.h", "netcsum_tune.h"]
 
 
 def src_sha(kernel_name):

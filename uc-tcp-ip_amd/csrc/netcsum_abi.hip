@@ -399,7 +399,7 @@ NET_ERR nchost::launch_batch(const Tune& t, const netcsum::SegBatchArgs& a0, uin
             const int depth = (ch == 4 || ch == 8) ? ch : ((plan & 4u) ? 8 : 4);
             a.plan_out = d_word;
             a.plan_tag = tag;
-            NC_HIP(netcsum::launch_live_varlen(a, depth, spw, s));
+            NC_HIP(netcsum::launch_live_varlen(t, a, depth, spw, s));
             char d[192];
             snprintf(d, sizeof d, "seg_live_varlen_kernel<D=%d%s,nt> block=256 segs_per_wave=%u plan=pool(live)%s", depth,
                      (a.pseudo && a.pseudo_len) ? ",pseudo" : "", spw, ahead);
@@ -413,7 +413,7 @@ NET_ERR nchost::launch_batch(const Tune& t, const netcsum::SegBatchArgs& a0, uin
             pipe.group = (plan & 3u) == 1u ? 16 : 8;      // plan 1: >= 1 KiB segments, 2: shorter
             pipe.chunks = (plan & 3u) == 1u ? 6 : 8;
             const netcsum::LaunchCfg cp = choose_cfg(pipe, dev, a0, len_hint);
-            NC_HIP(netcsum::launch_seg_batch(a, cp, s));
+            NC_HIP(netcsum::launch_seg_batch(pipe, a, cp, s));
             char d[192];
             snprintf(d, sizeof d, "%s plan=pool(pipe)%s", NetUtil_MI355X_LastLaunch(), ahead);
             netcsum::set_last_launch(d);
@@ -430,11 +430,11 @@ NET_ERR nchost::launch_batch(const Tune& t, const netcsum::SegBatchArgs& a0, uin
         NC_HIP(netcsum::launch_varlen_runlen(a.seg_off, a.seg_len_v, a.n_seg, a.pseudo ? a.pseudo_len : 0u, c.run_bytes,
                                              c.stream_spw, run, d_word, tag, s));
         a.run_dev = fixed ? nullptr : run;                 // (fixed runs: the sampler for the plan only)
-        NC_HIP(netcsum::launch_seg_batch(a, c, s));
+        NC_HIP(netcsum::launch_seg_batch(t, a, c, s));
         NC_HIP(word.end());
         return NET_UTIL_ERR_NONE;
     }
-    NC_HIP(netcsum::launch_seg_batch(a, c, s));
+    NC_HIP(netcsum::launch_seg_batch(t, a, c, s));
     return NET_UTIL_ERR_NONE;
 }
 
@@ -504,10 +504,10 @@ NET_ERR NetUtil_MI355X_CRC32BatchStrided(const void* d_base, uint64_t stride, ui
     a.n = n;
     a.cpl = cpl ? 1u : 0u;
     a.out = d_out;
-    netcsum::set_last_launch(netcsum::crc_launch_name(len, false));
+    netcsum::set_last_launch(netcsum::crc_launch_name(tls_tune, len, false));
     int dev = 0;
     NC_HIP(hipGetDevice(&dev));
-    NC_HIP(netcsum::launch_crc_batch(a, len, cu_count(dev), static_cast<hipStream_t>(hip_stream)));
+    NC_HIP(netcsum::launch_crc_batch(tls_tune, a, len, cu_count(dev), static_cast<hipStream_t>(hip_stream)));
     return NET_UTIL_ERR_NONE;
 }
 
@@ -522,10 +522,10 @@ NET_ERR NetUtil_MI355X_CRC32BatchVarLen(const void* d_base, const uint64_t* d_of
     a.n = n;
     a.cpl = cpl ? 1u : 0u;
     a.out = d_out;
-    netcsum::set_last_launch(netcsum::crc_launch_name(0xFFFFFFFFu, true));
+    netcsum::set_last_launch(netcsum::crc_launch_name(tls_tune, 0xFFFFFFFFu, true));
     int dev = 0;
     NC_HIP(hipGetDevice(&dev));
-    NC_HIP(netcsum::launch_crc_batch(a, 0xFFFFFFFFu, cu_count(dev), static_cast<hipStream_t>(hip_stream)));
+    NC_HIP(netcsum::launch_crc_batch(tls_tune, a, 0xFFFFFFFFu, cu_count(dev), static_cast<hipStream_t>(hip_stream)));
     return NET_UTIL_ERR_NONE;
 }
 
@@ -614,9 +614,9 @@ NET_ERR nchost::pkt_batch(const Tune& t, const PktJob& j) {
         netcsum::PktTxRecord* recs = rec_bytes ? reinterpret_cast<netcsum::PktTxRecord*>(static_cast<uint8_t*>(scratch.ptr()) + kHdr)
                                                : nullptr;
         if (j.rec_only != nullptr) {                      // zero-copy Tx burst: records only, no scatter
-            NC_HIP(netcsum::launch_pkt_stream(a, j.ip_ver, p.d, p.spw, p.snt, j.tx, p.bound, hs, j.rec_only, false));
+            NC_HIP(netcsum::launch_pkt_stream(t, a, j.ip_ver, p.d, p.spw, p.snt, j.tx, p.bound, hs, j.rec_only, false));
         } else {
-            NC_HIP(netcsum::launch_pkt_stream(a, j.ip_ver, p.d, p.spw, p.snt, j.tx, p.bound, hs, p.two ? recs : nullptr));
+            NC_HIP(netcsum::launch_pkt_stream(t, a, j.ip_ver, p.d, p.spw, p.snt, j.tx, p.bound, hs, p.two ? recs : nullptr));
         }
         if (a.vl_ctr != nullptr) scratch.tail_reset_enqueued();   // (launch_pkt_stream enqueued the deferred pass)
         NC_HIP(scratch.end());
@@ -713,12 +713,12 @@ NET_ERR NetUtil_MI355X_ChkSumBatchChains(const void* d_base, const uint64_t* d_p
             const int depth = ch == 4 ? 4 : 8;
             char d[128];
             if (one_rec) {
-                const bool cmp = netcsum::live_compact();
+                const bool cmp = netcsum::live_compact(t);
                 const int cl = t.chain_combine == 64 ? 64 : 16;
                 snprintf(d, sizeof d, "seg_live_varlen_kernel<D=%d,chain,nt%s> pieces_per_wave=%u +chain_combine_h_kernel<%d>",
                          depth, cmp ? ",compact" : "", live, cl);
                 netcsum::set_last_launch(d);
-                NC_HIP(netcsum::launch_chain_two_pass_h(a, static_cast<uint32_t*>(scratch.ptr()), (uint32_t)cap, cu_count(dev),
+                NC_HIP(netcsum::launch_chain_two_pass_h(t, a, static_cast<uint32_t*>(scratch.ptr()), (uint32_t)cap, cu_count(dev),
                                                         static_cast<hipStream_t>(hip_stream), live, depth, cmp, cl));
                 NC_HIP(scratch.end());
                 return NET_UTIL_ERR_NONE;
@@ -729,7 +729,7 @@ NET_ERR NetUtil_MI355X_ChkSumBatchChains(const void* d_base, const uint64_t* d_p
                 snprintf(d, sizeof d, "chain_piece_kernel<G=16,K=6,tile=64,nt> +chain_combine_kernel");
             }
             netcsum::set_last_launch(d);
-            NC_HIP(netcsum::launch_chain_two_pass(a, static_cast<uint64_t*>(scratch.ptr()), (uint32_t)cap, cu_count(dev),
+            NC_HIP(netcsum::launch_chain_two_pass(t, a, static_cast<uint64_t*>(scratch.ptr()), (uint32_t)cap, cu_count(dev),
                                                   static_cast<hipStream_t>(hip_stream), live, depth));
             NC_HIP(scratch.end());
             return NET_UTIL_ERR_NONE;
@@ -918,7 +918,7 @@ NET_ERR NetUtil_MI355X_ReadStream(const void* d_buf, uint64_t n_bytes, uint64_t*
     int dev = 0;
     NC_HIP(hipGetDevice(&dev));
     if (t.probe >= 2) {                     // run-stream form (netcsum_stream.hip); 3: with a pause per piece
-        NC_HIP(netcsum::launch_read_run(d_buf, n_bytes, reinterpret_cast<unsigned long long*>(d_sink),
+        NC_HIP(netcsum::launch_read_run(t, d_buf, n_bytes, reinterpret_cast<unsigned long long*>(d_sink),
                                         static_cast<hipStream_t>(hip_stream), t.probe == 3));
         return NET_UTIL_ERR_NONE;
     }
@@ -935,65 +935,65 @@ NET_ERR NetUtil_MI355X_PlanBind(uint32_t plan_id) {
 }
 
 // NetUtil_MI355X_Tune as a table: per key the accepted values (a range, or a listed set), a
-// normalisation of the accepted value where the key has one, and where it goes — a field of the
-// calling thread's Tune, or the knob a kernel file keeps beside its launcher.
+// normalisation of the accepted value where the key has one, and the field of the calling thread's Tune
+// it is stored in.
 namespace {
 constexpr int kEnd = INT_MIN;                           // ends a row's value set
 struct TuneRow {
     int key;
     int lo, hi;                                         // accepted range, unless
     int set[9];                                         // set[0] != kEnd: the accepted values, kEnd-terminated
-    int Tune::*field;                                   // stored here, or (nullptr)
-    void (*setter)(int);                                // handed to this setter
+    int Tune::*field;                                   // stored here
     int (*norm)(int);                                   // applied first to an accepted value (nullptr: as given)
 };
 const TuneRow kTuneRows[] = {
-    {NETCSUM_TUNE_GRID_BLOCKS, 0, INT_MAX, {kEnd}, &Tune::grid, nullptr, nullptr},
-    {NETCSUM_TUNE_GROUP_LANES, 0, 0, {0, 1, 4, 8, 16, 32, 64, kEnd}, &Tune::group, nullptr, nullptr},
-    {NETCSUM_TUNE_NT_LOADS, INT_MIN, INT_MAX, {kEnd}, &Tune::nt, nullptr, [](int v) { return v < 0 ? -1 : (int)(v != 0); }},
-    {NETCSUM_TUNE_BLOCK_THREADS, 0, 0, {0, 64, 128, 256, kEnd}, &Tune::block, nullptr,   // __launch_bounds__(256)
+    {NETCSUM_TUNE_GRID_BLOCKS, 0, INT_MAX, {kEnd}, &Tune::grid, nullptr},
+    {NETCSUM_TUNE_GROUP_LANES, 0, 0, {0, 1, 4, 8, 16, 32, 64, kEnd}, &Tune::group, nullptr},
+    {NETCSUM_TUNE_NT_LOADS, INT_MIN, INT_MAX, {kEnd}, &Tune::nt, [](int v) { return v < 0 ? -1 : (int)(v != 0); }},
+    {NETCSUM_TUNE_BLOCK_THREADS, 0, 0, {0, 64, 128, 256, kEnd}, &Tune::block,   // __launch_bounds__(256)
      [](int v) { return v == 0 ? 256 : v; }},
-    {NETCSUM_TUNE_KERNEL, 0, 8, {kEnd}, &Tune::kernel, nullptr, nullptr},
-    {NETCSUM_TUNE_CHUNKS, 0, 0, {0, 1, 2, 3, 4, 6, 8, kEnd}, &Tune::chunks, nullptr, nullptr},
-    {NETCSUM_TUNE_PROBE, 0, 3, {kEnd}, &Tune::probe, nullptr, nullptr},
-    {NETCSUM_TUNE_GRID_MULT, 0, 64, {kEnd}, &Tune::grid_mult, nullptr, [](int v) { return v == 0 ? 1 : v; }},
-    {NETCSUM_TUNE_TILE, -1, 1 << 20, {kEnd}, &Tune::tile, nullptr, nullptr},
-    {NETCSUM_TUNE_TX_PASSES, 0, 2, {kEnd}, &Tune::tx_passes, nullptr, nullptr},
-    {NETCSUM_TUNE_STREAM_WAVES, 0, 0, {-1, 0, 3, 4, 5, 6, 7, 8, kEnd}, nullptr, netcsum::set_stream_waves, nullptr},
-    {NETCSUM_TUNE_STREAM_TOUCH, -1, 1, {kEnd}, nullptr, netcsum::set_stream_touch, nullptr},
-    {NETCSUM_TUNE_STREAM_XCD, -1, 4096, {kEnd}, nullptr, netcsum::set_stream_xcd, nullptr},
-    {NETCSUM_TUNE_TX_FLUSH, -1, 4, {kEnd}, nullptr, netcsum::set_tx_flush, nullptr},
-    {NETCSUM_TUNE_CRC_KERNEL, 0, 3, {kEnd}, nullptr, netcsum::set_crc_kernel, nullptr},
-    {NETCSUM_TUNE_CRC_NT, 0, 1, {kEnd}, nullptr, netcsum::set_crc_nt, nullptr},
-    {NETCSUM_TUNE_CRC_LANES, 0, 0, {0, 1, 2, 4, 8, 16, kEnd}, nullptr, netcsum::set_crc_lanes, nullptr},
-    {NETCSUM_TUNE_CRC_WIDE, 0, 2, {kEnd}, nullptr, netcsum::set_crc_wide, nullptr},
-    {NETCSUM_TUNE_HDR_BURST, -1, 1, {kEnd}, nullptr, netcsum::set_hdr_burst, nullptr},
-    {NETCSUM_TUNE_VARLEN_RUN_BYTES, -1, 1 << 20, {kEnd}, nullptr, netcsum::set_varlen_run_bytes, nullptr},
-    {NETCSUM_TUNE_PKT_BOUND, -1, 4, {kEnd}, &Tune::pkt_bound, nullptr, nullptr},
-    {NETCSUM_TUNE_BURST_ZERO_COPY, 0, 3, {kEnd}, &Tune::burst_zc, nullptr, nullptr},
-    {NETCSUM_TUNE_BURST_SERVER_IDLE_US, 1, 1000000, {kEnd}, &Tune::burst_idle, nullptr, nullptr},
-    {NETCSUM_TUNE_BURST_SERVER_LIFE_US, 1, 1000000, {kEnd}, &Tune::burst_life, nullptr, nullptr},
-    {NETCSUM_TUNE_FAULT_INJECT, 0, 1, {kEnd}, nullptr, [](int v) { netcsum::set_fault_skip_deferred(v == 1); }, nullptr},
-    {NETCSUM_TUNE_PLAN_AHEAD, -1, 1, {kEnd}, &Tune::plan_ahead, nullptr, nullptr},
-    {NETCSUM_TUNE_LIVE_COMPACT, -1, 1, {kEnd}, nullptr, netcsum::set_live_compact, nullptr},
-    {NETCSUM_TUNE_STORE_GATHER, -1, 1, {kEnd}, nullptr, netcsum::set_store_gather, nullptr},
-    {NETCSUM_TUNE_CHAIN_GRID, -1, 16, {kEnd}, nullptr, netcsum::set_chain_grid, nullptr},
-    {NETCSUM_TUNE_CHAIN_COMBINE, 0, 0, {-1, 16, 64, kEnd}, &Tune::chain_combine, nullptr, nullptr},
+    {NETCSUM_TUNE_KERNEL, 0, 8, {kEnd}, &Tune::kernel, nullptr},
+    {NETCSUM_TUNE_CHUNKS, 0, 0, {0, 1, 2, 3, 4, 6, 8, kEnd}, &Tune::chunks, nullptr},
+    {NETCSUM_TUNE_PROBE, 0, 3, {kEnd}, &Tune::probe, nullptr},
+    {NETCSUM_TUNE_GRID_MULT, 0, 64, {kEnd}, &Tune::grid_mult, [](int v) { return v == 0 ? 1 : v; }},
+    {NETCSUM_TUNE_TILE, -1, 1 << 20, {kEnd}, &Tune::tile, nullptr},
+    {NETCSUM_TUNE_TX_PASSES, 0, 2, {kEnd}, &Tune::tx_passes, nullptr},
+    {NETCSUM_TUNE_STREAM_WAVES, 0, 0, {-1, 0, 3, 4, 5, 6, 7, 8, kEnd}, &Tune::stream_waves, nullptr},
+    {NETCSUM_TUNE_STREAM_TOUCH, -1, 1, {kEnd}, &Tune::stream_touch, nullptr},
+    {NETCSUM_TUNE_STREAM_XCD, -1, 4096, {kEnd}, &Tune::stream_xcd, nullptr},
+    {NETCSUM_TUNE_TX_FLUSH, -1, 4, {kEnd}, &Tune::tx_flush, nullptr},
+    {NETCSUM_TUNE_CRC_KERNEL, 0, 3, {kEnd}, &Tune::crc_kernel, nullptr},
+    {NETCSUM_TUNE_CRC_NT, 0, 1, {kEnd}, &Tune::crc_nt, nullptr},
+    {NETCSUM_TUNE_CRC_LANES, 0, 0, {0, 1, 2, 4, 8, 16, kEnd}, &Tune::crc_lanes, nullptr},
+    {NETCSUM_TUNE_CRC_WIDE, 0, 2, {kEnd}, &Tune::crc_wide, nullptr},
+    {NETCSUM_TUNE_HDR_BURST, -1, 1, {kEnd}, &Tune::hdr_burst, nullptr},
+    {NETCSUM_TUNE_VARLEN_RUN_BYTES, -1, 1 << 20, {kEnd}, &Tune::varlen_run_bytes, nullptr},
+    {NETCSUM_TUNE_PKT_BOUND, -1, 4, {kEnd}, &Tune::pkt_bound, nullptr},
+    {NETCSUM_TUNE_BURST_ZERO_COPY, 0, 3, {kEnd}, &Tune::burst_zc, nullptr},
+    {NETCSUM_TUNE_BURST_SERVER_IDLE_US, 1, 1000000, {kEnd}, &Tune::burst_idle, nullptr},
+    {NETCSUM_TUNE_BURST_SERVER_LIFE_US, 1, 1000000, {kEnd}, &Tune::burst_life, nullptr},
+    {NETCSUM_TUNE_PLAN_AHEAD, -1, 1, {kEnd}, &Tune::plan_ahead, nullptr},
+    {NETCSUM_TUNE_LIVE_COMPACT, -1, 1, {kEnd}, &Tune::live_compact, nullptr},
+    {NETCSUM_TUNE_STORE_GATHER, -1, 1, {kEnd}, &Tune::store_gather, nullptr},
+    {NETCSUM_TUNE_CHAIN_GRID, -1, 16, {kEnd}, &Tune::chain_grid, nullptr},
+    {NETCSUM_TUNE_CHAIN_COMBINE, 0, 0, {-1, 16, 64, kEnd}, &Tune::chain_combine, nullptr},
 };
 }  // namespace
 
 NET_ERR NetUtil_MI355X_Tune(int key, int value) {
+    // Not a setting, so not in Tune: a one-shot flag the test arms (1) or disarms (0) and the next deferred
+    // pass consumes, kept beside that launcher (netcsum_pktstream.hip launch_vl_deferred).
+    if (key == NETCSUM_TUNE_FAULT_INJECT) {
+        if (value != 0 && value != 1) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+        netcsum::set_fault_skip_deferred(value == 1);
+        return NET_UTIL_ERR_NONE;
+    }
     for (const TuneRow& r : kTuneRows) {
         if (r.key != key) continue;
         bool ok = r.set[0] == kEnd && value >= r.lo && value <= r.hi;
         for (int i = 0; !ok && r.set[0] != kEnd && r.set[i] != kEnd; ++i) ok = r.set[i] == value;
         if (!ok) break;
-        const int v = r.norm ? r.norm(value) : value;
-        if (r.field != nullptr) {
-            tls_tune.*r.field = v;
-        } else {
-            r.setter(v);
-        }
+        tls_tune.*r.field = r.norm ? r.norm(value) : value;
         return NET_UTIL_ERR_NONE;
     }
     return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;

@@ -857,9 +857,9 @@ __global__ void __launch_bounds__(256) chain_combine_h_kernel(ChainBatchArgs A, 
 
 }  // namespace
 
-hipError_t launch_chain_two_pass_h(const ChainBatchArgs& a, uint32_t* rec, uint32_t cap, int cus, hipStream_t s,
-                                   uint32_t spw, int depth, bool cmp, int combine_lanes) {
-    hipError_t e = launch_chain_live_records(a, rec, cap, depth, spw, cmp, s);
+hipError_t launch_chain_two_pass_h(const KernelTune& k, const ChainBatchArgs& a, uint32_t* rec, uint32_t cap, int cus,
+                                   hipStream_t s, uint32_t spw, int depth, bool cmp, int combine_lanes) {
+    hipError_t e = launch_chain_live_records(k, a, rec, cap, depth, spw, cmp, s);
     if (e != hipSuccess) return e;
     const uint32_t cg = combine_lanes == 64 ? 64u : 16u;
     const uint64_t blocks = ((uint64_t)a.n + 256u / cg - 1u) / (256u / cg);
@@ -872,19 +872,8 @@ hipError_t launch_chain_two_pass_h(const ChainBatchArgs& a, uint32_t* rec, uint3
     return hipGetLastError();
 }
 
-namespace {
-thread_local TuneKnob g_chain_grid{-1};                          // NETCSUM_TUNE_CHAIN_GRID
-}
-void set_chain_grid(int v) {
-    g_chain_grid.store(v);
-}
-int chain_grid() {
-    const int v = g_chain_grid.load();
-    return v < 0 ? 0 : v;
-}
-
-hipError_t launch_chain_two_pass(const ChainBatchArgs& a, uint64_t* eo, uint32_t cap, int cus, hipStream_t s, uint32_t live_spw,
-                                 int live_depth) {
+hipError_t launch_chain_two_pass(const KernelTune& k, const ChainBatchArgs& a, uint64_t* eo, uint32_t cap, int cus, hipStream_t s,
+                                 uint32_t live_spw, int live_depth) {
     if (live_spw != 0u) {                                          // pass 1 in the live-sector stream:
         const uint64_t waves = ((uint64_t)cap + live_spw - 1u) / live_spw;   // a wave per run of the most
         const dim3 g1((unsigned)((waves + 3u) / 4u));              // pieces the records hold; runs past
@@ -916,13 +905,13 @@ hipError_t launch_chain_two_pass(const ChainBatchArgs& a, uint64_t* eo, uint32_t
     const uint64_t g1 = std::min<uint64_t>(std::min<uint64_t>(((uint64_t)cap + 63u) / 64u, 1ull << 20),
                                            std::max<uint64_t>(resident, 2ull * a.n));
     ChainBatchArgs ax = a;
-    ax.xcd = stream_xcd_mode(1);
-    const int cg = chain_grid();
+    ax.xcd = stream_xcd_mode(k, 1);
+    const int cg = chain_grid(k);
     if (cg >= 1) {                                                 // balanced: cg x the resident blocks
-        ax.xcd = stream_xcd(false) ? 1u : 0u;
+        ax.xcd = stream_xcd(k, false) ? 1u : 0u;
         hipLaunchKernelGGL((chain_piece_kernel<true, false>), dim3((unsigned)(resident * (uint64_t)cg)), dim3(256), 0, s, ax,
                            eo, cap);
-    } else if (stream_touch(false)) {
+    } else if (stream_touch(k, false)) {
         hipLaunchKernelGGL((chain_piece_kernel<false, true>), dim3((unsigned)std::max<uint64_t>(g1, 1u)), dim3(256), 0, s, ax,
                            eo, cap);
     } else {

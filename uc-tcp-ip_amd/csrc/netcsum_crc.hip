@@ -37,7 +37,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
 #include <string>
 #include <vector>
 
@@ -704,15 +703,10 @@ uint32_t h_x8n(uint64_t n) {
     return p;
 }
 
-thread_local TuneKnob g_crc_kernel{0};      // NETCSUM_TUNE_CRC_KERNEL (netcsum_mi355x.h)
-thread_local TuneKnob g_crc_lanes{0};       // NETCSUM_TUNE_CRC_LANES: interleaved lanes per segment, 0 auto
-thread_local TuneKnob g_crc_nt{0};          // NETCSUM_TUNE_CRC_NT: non-temporal chunk loads (interleaved form)
-thread_local TuneKnob g_crc_wide{1};        // NETCSUM_TUNE_CRC_WIDE: 0 byte, 1 11-bit, 2 lane-replicated 6-bit tables
-
 enum class CrcForm { Lane, Block, Ilv1, Ilv2, Ilv4, Ilv8, Ilv16 };
 
-CrcForm ilv_form(uint32_t max_len, bool varlen) {
-    switch (g_crc_lanes.load()) {
+CrcForm ilv_form(const KernelTune& k, uint32_t max_len, bool varlen) {
+    switch (k.crc_lanes) {
     case 1: return CrcForm::Ilv1;
     case 2: return CrcForm::Ilv2;
     case 4: return CrcForm::Ilv4;
@@ -722,23 +716,18 @@ CrcForm ilv_form(uint32_t max_len, bool varlen) {
     }
 }
 
-CrcForm crc_form(uint32_t max_len, bool varlen) {
-    switch (g_crc_kernel.load()) {
+CrcForm crc_form(const KernelTune& k, uint32_t max_len, bool varlen) {
+    switch (k.crc_kernel) {
     case 1: return max_len <= kCrcShortMax && !varlen ? CrcForm::Lane : CrcForm::Block;
-    case 2: return ilv_form(max_len, varlen);
+    case 2: return ilv_form(k, max_len, varlen);
     case 3: return CrcForm::Lane;
-    default: return max_len <= kCrcShortMax && !varlen ? CrcForm::Lane : ilv_form(max_len, varlen);
+    default: return max_len <= kCrcShortMax && !varlen ? CrcForm::Lane : ilv_form(k, max_len, varlen);
     }
 }
 
 }  // namespace
 
-void set_crc_kernel(int v) { g_crc_kernel.store(v); }
-void set_crc_lanes(int v) { g_crc_lanes.store(v); }
-void set_crc_nt(int v) { g_crc_nt.store(v); }
-void set_crc_wide(int v) { g_crc_wide.store(v); }
-
-const char* crc_launch_name(uint32_t max_len, bool varlen) {
+const char* crc_launch_name(const KernelTune& k, uint32_t max_len, bool varlen) {
     // [table form][nt][log2 G]: "crc_ilv_kernel<nt,w11> G=4 block=512", ...
     static const std::vector<std::string> names = [] {
         std::vector<std::string> v;
@@ -754,9 +743,9 @@ const char* crc_launch_name(uint32_t max_len, bool varlen) {
         }
         return v;
     }();
-    const int w = std::min(std::max(g_crc_wide.load(), 0), 2);
-    const int base = 10 * w + (g_crc_nt.load() != 0 ? 5 : 0);
-    switch (crc_form(max_len, varlen)) {
+    const int w = std::min(std::max(k.crc_wide, 0), 2);
+    const int base = 10 * w + (k.crc_nt != 0 ? 5 : 0);
+    switch (crc_form(k, max_len, varlen)) {
     case CrcForm::Lane: return !varlen && max_len <= 16u ? "crc_tiny_kernel block=256" : "crc_lane_kernel block=256";
     case CrcForm::Block: return "crc_group_kernel G=16 block=256";
     case CrcForm::Ilv1: return names[base + 0].c_str();
@@ -768,14 +757,14 @@ const char* crc_launch_name(uint32_t max_len, bool varlen) {
 }
 
 template <int G, int W>
-static void launch_ilv_w(const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
+static void launch_ilv_w(const KernelTune& k, const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
     constexpr uint32_t B = ilv_block(W);
     const uint32_t steps = (a.n + (B / G) - 1u) / (B / G);
     // blocks resident per CU by LDS: byte tables 24 / 20 / <= 16 KiB (256 threads); W 1 44 .. 60 KiB
     // (512); W 2 85 .. 97 KiB (1024)
     const uint32_t per_cu = W == 2 ? 1u : W == 1 ? (G >= 8 ? 2u : 3u) : (G == 16 ? 6u : G == 8 ? 8u : 10u);
     const uint32_t grid = std::min<uint32_t>(steps, cu * per_cu);
-    if (g_crc_nt.load()) {
+    if (k.crc_nt) {
         hipLaunchKernelGGL((crc_ilv_kernel<G, true, W>), dim3(grid), dim3(B), 0, s, a);
     } else {
         hipLaunchKernelGGL((crc_ilv_kernel<G, false, W>), dim3(grid), dim3(B), 0, s, a);
@@ -783,20 +772,20 @@ static void launch_ilv_w(const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
 }
 
 template <int G>
-static void launch_ilv(const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
-    switch (g_crc_wide.load()) {
-    case 0: launch_ilv_w<G, 0>(a, cu, s); break;
-    case 2: launch_ilv_w<G, 2>(a, cu, s); break;
-    default: launch_ilv_w<G, 1>(a, cu, s); break;
+static void launch_ilv(const KernelTune& k, const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
+    switch (k.crc_wide) {
+    case 0: launch_ilv_w<G, 0>(k, a, cu, s); break;
+    case 2: launch_ilv_w<G, 2>(k, a, cu, s); break;
+    default: launch_ilv_w<G, 1>(k, a, cu, s); break;
     }
 }
 
-hipError_t launch_crc_batch(const CrcBatchArgs& a0, uint32_t max_len, int cus, hipStream_t s) {
+hipError_t launch_crc_batch(const KernelTune& k, const CrcBatchArgs& a0, uint32_t max_len, int cus, hipStream_t s) {
     if (a0.n == 0u) return hipSuccess;
     CrcBatchArgs a = a0;
     const uint32_t cu = (uint32_t)std::max(1, cus);
     const bool varlen = a.lens != nullptr;
-    switch (crc_form(max_len, varlen)) {
+    switch (crc_form(k, max_len, varlen)) {
     case CrcForm::Lane: {
         const uint32_t grid = std::min<uint32_t>((a.n + 255u) / 256u, cu * 8u);   // LDS 4 KiB per block
         if (!varlen && a.off == nullptr && a.len <= 16u) {
@@ -810,8 +799,8 @@ hipError_t launch_crc_batch(const CrcBatchArgs& a0, uint32_t max_len, int cus, h
         if (!varlen) {
             const uint32_t sb = ((a.len + kG * 4u - 1u) / (kG * 4u)) * 4u;
             uint32_t x = h_x8n(sb);
-            for (int k = 0; k < 4; ++k) {
-                a.xs[k] = x;
+            for (int j = 0; j < 4; ++j) {
+                a.xs[j] = x;
                 x = h_multmodp(x, x);
             }
             a.xl = h_x8n(a.len);
@@ -820,11 +809,11 @@ hipError_t launch_crc_batch(const CrcBatchArgs& a0, uint32_t max_len, int cus, h
         hipLaunchKernelGGL(crc_group_kernel, dim3(std::min<uint32_t>(steps, cu * 8u)), dim3(256), 0, s, a);
         break;
     }
-    case CrcForm::Ilv1: launch_ilv<1>(a, cu, s); break;
-    case CrcForm::Ilv2: launch_ilv<2>(a, cu, s); break;
-    case CrcForm::Ilv4: launch_ilv<4>(a, cu, s); break;
-    case CrcForm::Ilv8: launch_ilv<8>(a, cu, s); break;
-    default: launch_ilv<16>(a, cu, s); break;
+    case CrcForm::Ilv1: launch_ilv<1>(k, a, cu, s); break;
+    case CrcForm::Ilv2: launch_ilv<2>(k, a, cu, s); break;
+    case CrcForm::Ilv4: launch_ilv<4>(k, a, cu, s); break;
+    case CrcForm::Ilv8: launch_ilv<8>(k, a, cu, s); break;
+    default: launch_ilv<16>(k, a, cu, s); break;
     }
     return hipGetLastError();
 }

@@ -20,8 +20,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
@@ -156,27 +154,17 @@ __global__ void __launch_bounds__(256) seg_hdrstream_kernel(SegBatchArgs A, uint
     touch_retire(touch);
 }
 
-thread_local TuneKnob g_hdr_burst{-1};      // NETCSUM_TUNE_HDR_BURST: -1 default (kHdrBurstDefault), 0, 1
-constexpr bool kHdrBurstDefault = true;     // C3 0.0584 -> 0.0571-0.0575 ms (profiles/r2zi_c3_burst_sweep.jsonl)
-
-}  // namespace
-
-void set_hdr_burst(int v) { g_hdr_burst.store(v); }
-bool hdr_burst() { const int v = g_hdr_burst.load(); return v < 0 ? kHdrBurstDefault : v > 0; }
-
-namespace {
-
 template <int M, int D, bool NT>
-hipError_t launch_hs_t(const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
+hipError_t launch_hs_t(const KernelTune& k, const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
     SegBatchArgs a = a0;
-    a.touch = stream_touch(true) ? 1u : 0u;
-    a.xcd = stream_xcd(false) ? 1u : 0u;   // r2x: 0.0579-0.0584 ms off vs 0.0589 on
+    a.touch = stream_touch(k, true) ? 1u : 0u;
+    a.xcd = stream_xcd(k, false) ? 1u : 0u;   // r2x: 0.0579-0.0584 ms off vs 0.0589 on
     const uint64_t waves = ((uint64_t)a.n_seg + spw - 1u) / spw;
     const dim3 grid((unsigned)((waves + 3u) / 4u));
-    if (hdr_burst()) {
-        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, true>), grid, dim3(256), stream_lds_bytes(0), s, a, spw);
+    if (hdr_burst(k)) {
+        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
     } else {
-        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, false>), grid, dim3(256), stream_lds_bytes(0), s, a, spw);
+        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, false>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
     }
     return hipGetLastError();
 }
@@ -190,11 +178,11 @@ bool hdrstream_supported(const SegBatchArgs& a) {
            a.seg_stride == a.seg_len && ((uintptr_t)a.base & 3u) == 0u && a.n_seg < 0x7FFFFFFFu;
 }
 
-hipError_t launch_hdrstream(const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
+hipError_t launch_hdrstream(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
     if (!hdrstream_supported(a) || spw == 0u || spw > (1u << 20)) return hipErrorInvalidValue;
     const int m = (int)(a.seg_len / 4u);
 #define NETCSUM_HS(M_, D_, NT_) \
-    if (m == M_ && depth == D_ && nt == NT_) return launch_hs_t<M_, D_, NT_>(a, spw, s);
+    if (m == M_ && depth == D_ && nt == NT_) return launch_hs_t<M_, D_, NT_>(k, a, spw, s);
     NETCSUM_HS(5, 4, true) NETCSUM_HS(5, 4, false) NETCSUM_HS(5, 8, true) NETCSUM_HS(5, 8, false)
     NETCSUM_HS(4, 4, true) NETCSUM_HS(4, 4, false) NETCSUM_HS(4, 8, true) NETCSUM_HS(4, 8, false)
 #undef NETCSUM_HS

@@ -31,9 +31,9 @@ int cu_count(int dev);                                  // compute units of the 
 // The calling thread's launch options (NetUtil_MI355X_Tune, NetUtil_MI355X_PlanBind): one value per host
 // thread, so one thread's tuning never changes another thread's launches; a new thread starts from
 // these defaults. Only NetUtil_MI355X_Tune / _PlanBind store to it: every policy function takes it by
-// const reference, so what a launch depends on can be read off its signature. (The knobs of the
-// kernel files — set_stream_waves, set_crc_kernel, ... — live with their launchers.)
-struct Tune {
+// const reference, and every launcher that reads an option takes its KernelTune part (netcsum_tune.h)
+// the same way, so what a launch depends on can be read off its signature.
+struct Tune : netcsum::KernelTune {
     int grid = 0;
     int group = 0;
     int nt = -1;                    // -1: auto (nt when groups share no chunks)

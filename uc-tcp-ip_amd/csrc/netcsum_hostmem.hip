@@ -308,7 +308,7 @@ NET_ERR NetUtil_MI355X_CRC32Host(const void* h_data, uint32_t len, uint32_t* p_c
     a.len = len;
     a.n = 1;
     a.out = reinterpret_cast<uint32_t*>(c.d_sum);
-    NC_HIP(netcsum::launch_crc_batch(a, len, cu_count(c.dev), c.stream));
+    NC_HIP(netcsum::launch_crc_batch(tune(), a, len, cu_count(c.dev), c.stream));
     NC_HIP(hipMemcpyAsync(c.h_sum, c.d_sum, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
     NC_HIP(hipStreamSynchronize(c.stream));
     *p_crc = *reinterpret_cast<volatile uint32_t*>(c.h_sum);
@@ -340,6 +340,7 @@ NET_ERR NetUtil_MI355X_ChkSumBatchStridedHost(const void* h_seg, uint64_t seg_st
     PipeDrainOnExit guard{c};
     int dev = 0;
     NC_HIP(hipGetDevice(&dev));
+    const Tune& t = tune();
     for (size_t k = 0; k < ch.size(); ++k) {
         const HostChunk& q = ch[k];
         hipStream_t st = c.pstream[k % 3u];
@@ -353,7 +354,7 @@ NET_ERR NetUtil_MI355X_ChkSumBatchStridedHost(const void* h_seg, uint64_t seg_st
                                                  pseudo_stride, has_ph ? pseudo_len : 0u, q.ns, op, d + o_out);
         // Parity of each segment's start is derived in-kernel from the DEVICE address it reads,
         // so re-basing the chunk at a 256-B aligned device buffer is transparent.
-        NC_HIP(netcsum::launch_seg_batch(a, choose_cfg(tune(), dev, a, seg_len), st));
+        NC_HIP(netcsum::launch_seg_batch(t, a, choose_cfg(t, dev, a, seg_len), st));
         NC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(h_out) + (size_t)q.s0 * out_elt, d + o_out, (size_t)q.ns * out_elt,
                               hipMemcpyDeviceToHost, st));
     }

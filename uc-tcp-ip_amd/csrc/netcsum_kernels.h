@@ -1,19 +1,16 @@
-// netcsum_kernels.h — internal interface between the C ABI (netcsum_abi.hip) and the kernels.
+// netcsum_kernels.h — internal interface between the C ABI (netcsum_abi.hip) and the kernels: the
+// argument blocks several kernel files share, then each kernel file's declarations in a section of its
+// own. A launcher that reads a launch option takes the caller's KernelTune (netcsum_tune.h) first.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "netcsum_tune.h"
+
 namespace netcsum {
 
-// A launch option (NetUtil_MI355X_Tune): one value per calling host thread, so one thread's tuning
-// never changes another thread's launches; a new thread starts from the defaults.
-struct TuneKnob {
-    int v;
-    template <class... A>
-    int load(A...) const { return v; }
-    void store(int x) { v = x; }
-};
+// ---- argument blocks shared by several kernel files
 
 struct SegBatchArgs {
     const uint8_t*  base;          // strided: first segment; varlen: base of the offsets
@@ -105,10 +102,6 @@ struct PktBatchArgs {
 constexpr uint32_t kFragSumWalk = 1u;
 constexpr uint32_t kFieldIP = 1u << 31;    // fieldpos_out: the IPv4 header checksum field (+10) written
 constexpr uint32_t kFieldL4 = 1u << 30;    // fieldpos_out: the transport field at (bits 0-15) written
-// One 8-B record per packet of a host-memory Tx batch (pkt_field_gather_kernel): the written field
-// values as they lie in memory (IP | transport << 16), the transport offset << 32, and the
-// kFieldIP / kFieldL4 bits << 32 (bits 62 / 63).
-hipError_t launch_pkt_field_gather(const PktBatchArgs& a, uint64_t* rec_out, hipStream_t s);
 
 // Tx UDP checksum policy of a datagram whose checksum field holds `field` (PktBatchArgs::udp_tx_csum).
 __host__ __device__ __forceinline__ bool udp_tx_compute(uint32_t mode, uint32_t field) {
@@ -138,28 +131,73 @@ struct ChainBatchArgs {
     uint32_t        xcd;           // pass 1: XCD-aware tile order (set by the launcher)
 };
 
+// ---- netcsum_kernels.hip: the lane-group segment kernels, the dispatch of a segment batch, the probes
+bool tile_supported(int g, int p, int k);   // is (G, P, K) a compiled v4 instantiation
+const char* last_launch();                  // description of this thread's last batch launch
+void set_last_launch(const char* desc);
+hipError_t launch_seg_batch(const KernelTune& k, const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s);
+hipError_t launch_stream_exact(const void* d_p, uint32_t n16, unsigned long long* d_sum, int grid,
+                               hipStream_t s, uint32_t tag = 0u);   // tag != 0 (grid 1): completion word
+hipError_t launch_fill(void* d_buf, uint64_t n_bytes, uint64_t first_byte, uint64_t seed, int pattern, int grid,
+                       hipStream_t s);
+hipError_t launch_read_stream(const void* d_p, uint64_t n16, unsigned long long* d_sink, int grid, bool nt,
+                              hipStream_t s, int variant);
+
+// ---- netcsum_small.hip
+bool small_supported(const SegBatchArgs& a);  // strided, no pseudo, 1..64 B, base/stride 4-B aligned
+hipError_t launch_small_batch(const SegBatchArgs& a, int grid, hipStream_t s);
+
+// ---- netcsum_hdr.hip
+bool hdr_supported(const SegBatchArgs& a);     // small_supported and stride <= 64: LDS-image header tiles
+int hdr_lanes_h(const SegBatchArgs& a, int h);  // headers per lane kernel 7 uses for a request (auto: h <= 0)
+uint32_t hdr_pieces(const SegBatchArgs& a, int h);   // 1-KiB LDS-DMA pieces per tile of 64*h headers
+int hdr_occupancy(const SegBatchArgs& a, int stages, int h);
+hipError_t launch_hdr_batch(const SegBatchArgs& a, int stages, int h, int grid, hipStream_t s);
+
+// ---- netcsum_hdrstream.hip
+bool hdrstream_supported(const SegBatchArgs& a);                  // kernel 8: packed 16 / 20-B headers
+hipError_t launch_hdrstream(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s);
+
+// ---- netcsum_stream.hip
+bool stream_supported(const SegBatchArgs& a);  // strided, stride in [len, len+64], len >= 256
+bool stream_dense(const SegBatchArgs& a);      // strided, stride == len >= 1024: the default for kernel 6
+uint32_t stream_spw(const SegBatchArgs& a, uint64_t waves);
+int stream_occupancy(int depth, const SegBatchArgs& a, bool nt);   // resident 256-thread blocks per CU
+hipError_t launch_stream_batch(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s);
+// Varlen run length from sampled lengths: *out = clamp(run_bytes / (mean length + extra), spw_min, 128);
+// with plan_out, also the batch's plan there: 1 << 31 | tag << 16 | form (0 the stream kernel; 1 / 2
+// the lane-group pipe at 16 x 6 / 8 x 8, for sparse pools; 3 the live-sector stream, run << 8, bit 2
+// depth 8).
+hipError_t launch_varlen_runlen(const uint64_t* offs, const uint16_t* lens, uint32_t n, uint32_t extra, uint32_t run_bytes,
+                                uint32_t spw_min, uint32_t* out, uint32_t* plan_out, uint32_t tag, hipStream_t s);
+// Segments one per pool buffer (plan 3): the live-sector stream (netcsum_stream.hip
+// seg_live_varlen_kernel), runs of spw <= 64 segments, depth 4 or 8 pieces in flight; a.plan_out:
+// one extra block samples the descriptors for the next batch's plan.
+hipError_t launch_live_varlen(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, hipStream_t s);
+constexpr uint32_t kVarlenSpwMin = 3u;
+// Chain pass 1 in the live-sector segment stream (seg_live_varlen_kernel<…, CH>): runs of spw (<= 64)
+// consecutive pieces, depth (4 / 8) pieces in flight, compacted sectors when cmp; each piece's exact
+// half-word sum (u32, absolute LE frame) into rec[j]. (With the combine pass over those records:
+// launch_chain_two_pass_h, netcsum_chains.hip.)
+hipError_t launch_chain_live_records(const KernelTune& k, const ChainBatchArgs& c, uint32_t* rec, uint32_t cap, int depth,
+                                     uint32_t spw, bool cmp, hipStream_t s);
+hipError_t launch_read_run(const KernelTune& k, const void* d_p, uint64_t n_bytes, unsigned long long* d_sink, hipStream_t s,
+                           bool sleep);
+
+// ---- netcsum_chains.hip
 hipError_t launch_chain_batch(const ChainBatchArgs& a, int group, int grid, hipStream_t s);
 // Two-pass form (default): per-piece even/odd sums into `eo` (cap records), then a combine pass per
 // chain; batches of more than `cap` pieces fall back to the wave-per-chain form inside pass 2.
 // live_spw != 0: pass 1 in the live-sector stream, runs of live_spw (<= 64) consecutive pieces,
 // live_depth (4 / 8) pieces in flight.
-// NETCSUM_TUNE_CHAIN_GRID: 0 / -1 pass 1 in tiles of 64 pieces, one per block; k >= 1 a grid of k x the
-// resident blocks, each owning an equal contiguous share of the pieces
-void set_chain_grid(int v);
-int chain_grid();
-hipError_t launch_chain_two_pass(const ChainBatchArgs& a, uint64_t* eo, uint32_t cap, int cus, hipStream_t s,
+hipError_t launch_chain_two_pass(const KernelTune& k, const ChainBatchArgs& a, uint64_t* eo, uint32_t cap, int cus, hipStream_t s,
                                  uint32_t live_spw = 0u, int live_depth = 8);
-// Chain pass 1 in the live-sector segment stream (seg_live_varlen_kernel<…, CH>, netcsum_stream.hip):
-// runs of spw (<= 64) consecutive pieces, depth (4 / 8) pieces in flight, compacted sectors when cmp;
-// each piece's exact half-word sum (u32, absolute LE frame) into rec[j]. Then the combine pass over
-// those records (chain_combine_h_kernel, netcsum_chains.hip); the two together:
-hipError_t launch_chain_live_records(const ChainBatchArgs& c, uint32_t* rec, uint32_t cap, int depth, uint32_t spw, bool cmp,
-                                     hipStream_t s);
-// combine_lanes: 16 or 64 lanes per chain in the combine pass
-hipError_t launch_chain_two_pass_h(const ChainBatchArgs& a, uint32_t* rec, uint32_t cap, int cus, hipStream_t s,
-                                   uint32_t spw, int depth, bool cmp, int combine_lanes);
+// launch_chain_live_records (netcsum_stream.hip), then the combine pass over its records
+// (chain_combine_h_kernel); combine_lanes: 16 or 64 lanes per chain in the combine pass
+hipError_t launch_chain_two_pass_h(const KernelTune& k, const ChainBatchArgs& a, uint32_t* rec, uint32_t cap, int cus,
+                                   hipStream_t s, uint32_t spw, int depth, bool cmp, int combine_lanes);
 
-// CRC-32 batches (netcsum_crc.hip; net_util.c:485-636).
+// ---- netcsum_crc.hip: CRC-32 batches (net_util.c:485-636)
 struct CrcBatchArgs {
     const uint8_t*  base;          // segment i at base + off[i] (varlen) or base + i * stride
     const uint64_t* off;           // nullptr => strided
@@ -173,62 +211,25 @@ struct CrcBatchArgs {
     uint32_t        xl;            // strided: x^(8 len) mod P
 };
 constexpr uint32_t kCrcShortMax = 96u;     // strided segments up to this length: one lane each
-hipError_t launch_crc_batch(const CrcBatchArgs& a, uint32_t max_len, int cus, hipStream_t s);
-const char* crc_launch_name(uint32_t max_len, bool varlen);
-void set_crc_kernel(int v);    // NETCSUM_TUNE_CRC_KERNEL
-void set_crc_nt(int v);        // NETCSUM_TUNE_CRC_NT
-void set_crc_lanes(int v);     // NETCSUM_TUNE_CRC_LANES
-void set_crc_wide(int v);      // NETCSUM_TUNE_CRC_WIDE
+hipError_t launch_crc_batch(const KernelTune& k, const CrcBatchArgs& a, uint32_t max_len, int cus, hipStream_t s);
+const char* crc_launch_name(const KernelTune& k, uint32_t max_len, bool varlen);
 
+// ---- netcsum_packets.hip
 hipError_t launch_pkt_batch(const PktBatchArgs& a, const LaunchCfg& c, bool tx, int ip_ver,  // 4, 6, 0 = per packet
                             hipStream_t s);
 
-bool tile_supported(int g, int p, int k);   // is (G, P, K) a compiled v4 instantiation
-const char* last_launch();                  // description of this thread's last batch launch
-
-hipError_t launch_seg_batch(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s);
-bool small_supported(const SegBatchArgs& a);  // strided, no pseudo, 1..64 B, base/stride 4-B aligned
-hipError_t launch_small_batch(const SegBatchArgs& a, int grid, hipStream_t s);
-bool hdr_supported(const SegBatchArgs& a);     // small_supported and stride <= 64: LDS-image header tiles
-int hdr_lanes_h(const SegBatchArgs& a, int h);  // headers per lane kernel 7 uses for a request (auto: h <= 0)
-uint32_t hdr_pieces(const SegBatchArgs& a, int h);   // 1-KiB LDS-DMA pieces per tile of 64*h headers
-int hdr_occupancy(const SegBatchArgs& a, int stages, int h);
-bool hdrstream_supported(const SegBatchArgs& a);                  // kernel 8: packed 16 / 20-B headers
-hipError_t launch_hdrstream(const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s);
-// Varlen run length from sampled lengths: *out = clamp(run_bytes / (mean length + extra), spw_min, 128);
-// with plan_out, also the batch's plan there: 1 << 31 | tag << 16 | form (0 the stream kernel; 1 / 2
-// the lane-group pipe at 16 x 6 / 8 x 8, for sparse pools; 3 the live-sector stream, run << 8, bit 2
-// depth 8).
-hipError_t launch_varlen_runlen(const uint64_t* offs, const uint16_t* lens, uint32_t n, uint32_t extra, uint32_t run_bytes,
-                                uint32_t spw_min, uint32_t* out, uint32_t* plan_out, uint32_t tag, hipStream_t s);
-// Segments one per pool buffer (plan 3): the live-sector stream (netcsum_stream.hip
-// seg_live_varlen_kernel), runs of spw <= 64 segments, depth 4 or 8 pieces in flight; a.plan_out:
-// one extra block samples the descriptors for the next batch's plan.
-hipError_t launch_live_varlen(const SegBatchArgs& a, int depth, uint32_t spw, hipStream_t s);
-void set_varlen_run_bytes(int v);   // NETCSUM_TUNE_VARLEN_RUN_BYTES
-// NETCSUM_TUNE_LIVE_COMPACT: the live-sector streams read their live sectors compacted, 16 per
-// wave-instruction (-1 default / 1), or as the live 1-KiB pieces of their span (0)
-void set_live_compact(int v);
-bool live_compact();
-// NETCSUM_TUNE_STORE_GATHER: the dense segment stream kernel's results, per block of 4 runs, gathered in
-// LDS and stored whole by the block's last wave (-1 default / 1), or per wave (0)
-void set_store_gather(int v);
-bool store_gather();
-uint32_t varlen_run_bytes();
-constexpr uint32_t kVarlenSpwMin = 3u;
-void set_hdr_burst(int v);     // NETCSUM_TUNE_HDR_BURST: header stream results written per run (1) or per piece (0)
-bool hdr_burst();
+// ---- netcsum_pktstream.hip
+// One 8-B record per packet of a host-memory Tx batch (pkt_field_gather_kernel): the written field
+// values as they lie in memory (IP | transport << 16), the transport offset << 32, and the
+// kFieldIP / kFieldL4 bits << 32 (bits 62 / 63).
+hipError_t launch_pkt_field_gather(const PktBatchArgs& a, uint64_t* rec_out, hipStream_t s);
 bool pkt_stream_supported(const PktBatchArgs& a, int ip_ver, int bound);   // run-stream packet kernel's domain
-// Tx finalize write-back of the dirty field lines (NETCSUM_TUNE_TX_FLUSH): -1 / 0 none, 1 scatter
-// stores at system scope, 2 release at the end of every scatter wave, 3 / 4 a write-back launch of
-// 8 / 256 workgroups after the Tx launch(es).
-void set_tx_flush(int mode);
 // bound (NETCSUM_TUNE_PKT_BOUND): 0 every piece of the run's span, 1 / 2 / 3 the live pieces, with 0 / 1
 // / depth pieces loaded during the parse (netcsum_pktstream.hip; depth 8: bounds 0, 2 and 3)
 // rec: two-pass Tx (records + scatter); scatter = false: the records only (zero-copy host bursts, whose
 // host applies them)
-hipError_t launch_pkt_stream(const PktBatchArgs& a, int ip_ver, int depth, uint32_t spw, bool nt, bool tx, int bound,
-                             hipStream_t s, PktTxRecord* rec = nullptr, bool scatter = true);
+hipError_t launch_pkt_stream(const KernelTune& k, const PktBatchArgs& a, int ip_ver, int depth, uint32_t spw, bool nt, bool tx,
+                             int bound, hipStream_t s, PktTxRecord* rec = nullptr, bool scatter = true);
 // The ring plan's sampler alone (one block; a.plan, a.plan_out and the batch's descriptors / stride as
 // for the batch): the plan word for the batch about to be launched, which the host waits for.
 hipError_t launch_pkt_plan(const PktBatchArgs& a, int ip_ver, hipStream_t s);
@@ -288,9 +289,13 @@ struct BurstServerArgs {
 };
 // blocks x 256 threads on stream s (a stream of its own: the kernel runs until it is idle)
 hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t s);
+
+// ---- netcsum_v6walk.hip
 // IPv6 extension-header chains past the batch kernels' window (flags EXT_HDR): walked to the end and
 // finished in place (netcsum_v6walk.hip); a.flags_out holds the batch kernel's flags.
 hipError_t launch_pkt_v6_walk(const PktBatchArgs& a, bool tx, int cus, hipStream_t s);
+
+// ---- netcsum_ether.hip
 // The 802.x demux ahead of an Rx burst of Ethernet frames (netcsum_ether.hip ether_demux_kernel; the
 // rules: include/netcsum_ether.h): per frame its layer-2 class and the offset/length descriptor of the IP
 // datagram the packet batch is to check ({frame start, 0} for a frame that carries none).
@@ -312,37 +317,5 @@ struct EtherDemuxArgs {
 constexpr uint32_t kEtherDemuxBlock = 256u;
 inline uint32_t ether_demux_blocks(uint32_t n) { return (n + kEtherDemuxBlock - 1u) / kEtherDemuxBlock; }
 hipError_t launch_ether_demux(const EtherDemuxArgs& a, hipStream_t s);
-void set_last_launch(const char* desc);
-hipError_t launch_hdr_batch(const SegBatchArgs& a, int stages, int h, int grid, hipStream_t s);
-bool stream_supported(const SegBatchArgs& a);  // strided, stride in [len, len+64], len >= 256
-bool stream_dense(const SegBatchArgs& a);      // strided, stride == len >= 1024: the default for kernel 6
-uint32_t stream_spw(const SegBatchArgs& a, uint64_t waves);
-int stream_occupancy(int depth, const SegBatchArgs& a, bool nt);   // resident 256-thread blocks per CU
-hipError_t launch_stream_batch(const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s);
-// Residency cap of the run-stream kernels (NETCSUM_TUNE_STREAM_WAVES, -1 = each kernel's default):
-// LDS bytes each 256-thread workgroup reserves so that at most w of them (w waves per SIMD) fit a
-// CU's 160 KiB; 0 = no cap.
-void set_stream_waves(int w);
-uint32_t stream_lds_bytes(int auto_waves);
-bool stream_waves_tuned();             // NETCSUM_TUNE_STREAM_WAVES set (>= 0)
-// Row-touch prologue of the run-stream kernels (NETCSUM_TUNE_STREAM_TOUCH: -1 each kernel's
-// default `auto_on`, 0 off, 1 on).
-void set_stream_touch(int t);
-bool stream_touch(bool auto_on);
-// XCD-aware block order of the segment / varlen / header stream kernels (NETCSUM_TUNE_STREAM_XCD:
-// -1 each kernel's default `auto_on`, 0 off, 1 on). Measured (profiles/r2w_*, r2x_*): C5 shard
-// 3.614 -> 3.561 ms, C2 0.2186 -> 0.2181, C4 0.6777 -> 0.6747 (on); C3 0.0579-0.0584 -> 0.0589 (off).
-void set_stream_xcd(int on);
-bool stream_xcd(bool auto_on);
-// the block-order mode for xcd_block (netcsum_stream.h): 0 dispatch order, 1 one slice per XCD, C >= 2
-// chunks of C blocks per XCD in turn; auto_mode when the knob is at its default (-1)
-uint32_t stream_xcd_mode(uint32_t auto_mode);
-hipError_t launch_stream_exact(const void* d_p, uint32_t n16, unsigned long long* d_sum, int grid,
-                               hipStream_t s, uint32_t tag = 0u);   // tag != 0 (grid 1): completion word
-hipError_t launch_fill(void* d_buf, uint64_t n_bytes, uint64_t first_byte, uint64_t seed, int pattern, int grid,
-                       hipStream_t s);
-hipError_t launch_read_stream(const void* d_p, uint64_t n16, unsigned long long* d_sink, int grid, bool nt,
-                              hipStream_t s, int variant);
-hipError_t launch_read_run(const void* d_p, uint64_t n_bytes, unsigned long long* d_sink, hipStream_t s, bool sleep);
 
 }  // namespace netcsum

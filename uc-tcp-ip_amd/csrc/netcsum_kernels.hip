@@ -968,13 +968,13 @@ void set_last_launch(const char* desc) {
     snprintf(g_last_launch, sizeof(g_last_launch), "%s", desc);
 }
 
-static void note_launch(const LaunchCfg& c, const SegBatchArgs& a) {
+static void note_launch(const KernelTune& k, const LaunchCfg& c, const SegBatchArgs& a) {
     static const char* names[] = {"?", "seg_batch_kernel", "seg_pipe_kernel", "seg_lds_kernel", "seg_tile_kernel",
                                   "seg_small_kernel", "seg_stream_kernel", "seg_hdr_kernel", "seg_hdrstream_kernel"};
     const int kid = (c.kernel >= 1 && c.kernel <= 8) ? c.kernel : 0;
     if (kid == 8) {
         snprintf(g_last_launch, sizeof(g_last_launch), "seg_hdrstream_kernel<M=%u,D=%d%s%s> block=256 hdrs_per_wave=%u",
-                 a.seg_len / 4u, c.chunks_per_pass, c.nt ? ",nt" : "", hdr_burst() ? ",burst" : "", c.stream_spw);
+                 a.seg_len / 4u, c.chunks_per_pass, c.nt ? ",nt" : "", hdr_burst(k) ? ",burst" : "", c.stream_spw);
         return;
     }
     if (kid == 7) {
@@ -1005,21 +1005,21 @@ static void note_launch(const LaunchCfg& c, const SegBatchArgs& a) {
              c.nt ? ",nt" : "", "", c.block, c.tile, c.grid, c.tile_pieces);
 }
 
-hipError_t launch_seg_batch(const SegBatchArgs& args, const LaunchCfg& c, hipStream_t s) {
-    note_launch(c, args);
+hipError_t launch_seg_batch(const KernelTune& k, const SegBatchArgs& args, const LaunchCfg& c, hipStream_t s) {
+    note_launch(k, c, args);
     SegBatchArgs a = args;
     a.tile = c.tile > 0 ? (uint32_t)c.tile : 0u;
     if (c.kernel == 5) {
         return launch_small_batch(a, c.grid, s);              // K = dwords per segment
     }
     if (c.kernel == 6) {
-        return launch_stream_batch(a, c.chunks_per_pass, c.stream_spw, c.nt, s);   // K = pieces in flight
+        return launch_stream_batch(k, a, c.chunks_per_pass, c.stream_spw, c.nt, s);   // K = pieces in flight
     }
     if (c.kernel == 7) {
         return launch_hdr_batch(a, c.chunks_per_pass, c.tile, c.grid, s);                 // K = tiles in flight
     }
     if (c.kernel == 8) {
-        return launch_hdrstream(a, c.chunks_per_pass, c.stream_spw, c.nt, s);            // K = pieces in flight
+        return launch_hdrstream(k, a, c.chunks_per_pass, c.stream_spw, c.nt, s);         // K = pieces in flight
     }
     if (c.kernel == 4) {
         return launch_tile_dispatch(a, c, s);
@@ -1040,9 +1040,9 @@ hipError_t launch_seg_batch(const SegBatchArgs& args, const LaunchCfg& c, hipStr
         return c.nt ? launch_pipe_g<false, true>(a, c.group_lanes, c.chunks_per_pass, c, s)
                     : launch_pipe_g<false, false>(a, c.group_lanes, c.chunks_per_pass, c, s);
     }
-    const int k = c.chunks_per_pass > 4 ? 4 : c.chunks_per_pass;
-    return a.seg_off ? launch_seg_g<true>(a, c.group_lanes, k, c, c.nt, s)
-                     : launch_seg_g<false>(a, c.group_lanes, k, c, c.nt, s);
+    const int chunks = c.chunks_per_pass > 4 ? 4 : c.chunks_per_pass;
+    return a.seg_off ? launch_seg_g<true>(a, c.group_lanes, chunks, c, c.nt, s)
+                     : launch_seg_g<false>(a, c.group_lanes, chunks, c, c.nt, s);
 }
 
 hipError_t launch_stream_exact(const void* d_p, uint32_t n16, unsigned long long* d_sum, int grid,

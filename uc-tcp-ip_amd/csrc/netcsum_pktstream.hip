@@ -1150,16 +1150,9 @@ __global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
     }
 }
 
-thread_local TuneKnob g_tx_flush{-1};
-
-int tx_flush_mode() {
-    const int m = g_tx_flush.load(std::memory_order_relaxed);
-    return m < 0 ? 0 : m;
-}
-
 template <bool WALK>
-hipError_t launch_scatter(const PktBatchArgs& a, const PktTxRecord* rec, hipStream_t s) {
-    const int m = tx_flush_mode();
+hipError_t launch_scatter(const KernelTune& k, const PktBatchArgs& a, const PktTxRecord* rec, hipStream_t s) {
+    const int m = tx_flush_mode(k);
     const dim3 g((a.n + 255u) / 256u), b(256);
     if (m == 1) {
         hipLaunchKernelGGL((pkt_scatter_kernel<true, false, WALK>), g, b, 0, s, a, rec);
@@ -1171,8 +1164,8 @@ hipError_t launch_scatter(const PktBatchArgs& a, const PktTxRecord* rec, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_tx_flush(hipStream_t s) {
-    const int m = tx_flush_mode();
+hipError_t launch_tx_flush(const KernelTune& k, hipStream_t s) {
+    const int m = tx_flush_mode(k);
     if (m == 3 || m == 4) {
         hipLaunchKernelGGL(l2_writeback_kernel, dim3(m == 3 ? 8 : 256), dim3(64), 0, s);
         return hipGetLastError();
@@ -1194,15 +1187,16 @@ hipError_t launch_vl_deferred(const PktBatchArgs& a, int dgrid, uint32_t spw, Pk
 }
 
 template <int D, bool NT, bool TX, int VER, int BND, bool VL, bool SUMS = false>
-hipError_t launch_pkt_stream_t(const PktBatchArgs& a0, uint32_t spw, hipStream_t s, PktTxRecord* rec, bool scatter) {
+hipError_t launch_pkt_stream_t(const KernelTune& k, const PktBatchArgs& a0, uint32_t spw, hipStream_t s, PktTxRecord* rec,
+                               bool scatter) {
     PktBatchArgs a = a0;
     // no piece touch by default: the header prologue already loads each packet's first bytes with
     // the plain policy, and touching every piece on top is slower (r2ct: Rx 0.2174 -> 0.2315 ms)
-    a.touch = stream_touch(false) ? 1u : 0u;
-    a.xcd = stream_xcd(false) ? 1u : 0u;
+    a.touch = stream_touch(k, false) ? 1u : 0u;
+    a.xcd = stream_xcd(k, false) ? 1u : 0u;
     const uint64_t waves = ((uint64_t)a.n + spw - 1u) / spw;
     const int grid = (int)((waves + 3u) / 4u) + (a.plan_out != nullptr ? 1 : 0);   // (+ the plan block)
-    const uint32_t lds = stream_lds_bytes((int)a.res_waves);
+    const uint32_t lds = stream_lds_bytes(k, (int)a.res_waves);
     // offset/length: the deferred pass (8 blocks for a ring in order, else up to one per CU: a batch
     // whose every run is listed is slow, but correct)
     const int dgrid = a.vl_wide ? (int)std::min<uint64_t>((waves + 3u) / 4u, 2048u) : (int)std::min<uint64_t>((waves + 3u) / 4u, 8u);
@@ -1219,8 +1213,8 @@ hipError_t launch_pkt_stream_t(const PktBatchArgs& a0, uint32_t spw, hipStream_t
             }
         }
         if (e != hipSuccess || !scatter) return e;
-        e = launch_scatter<VER != 4>(a, rec, s);
-        return e != hipSuccess ? e : launch_tx_flush(s);
+        e = launch_scatter<VER != 4>(k, a, rec, s);
+        return e != hipSuccess ? e : launch_tx_flush(k, s);
     }
     if (VL && a.vl_ctr == nullptr) {
         hipLaunchKernelGGL((pkt_stream_kernel<D, NT, TX, false, VER, BND, VL, false, SUMS>), dim3(grid), dim3(256), lds, s, a, spw, rec);
@@ -1233,7 +1227,7 @@ hipError_t launch_pkt_stream_t(const PktBatchArgs& a0, uint32_t spw, hipStream_t
             e = launch_vl_deferred<D, NT, TX, false, VER, BND, SUMS>(a, dgrid, spw, rec, s);
         }
     }
-    return (e != hipSuccess || !TX) ? e : launch_tx_flush(s);
+    return (e != hipSuccess || !TX) ? e : launch_tx_flush(k, s);
 }
 
 }  // namespace
@@ -1263,10 +1257,6 @@ hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t
     return hipGetLastError();
 }
 
-void set_tx_flush(int mode) {
-    g_tx_flush.store(mode);
-}
-
 // Strided batches of >= 64-B packets (IPv4, IPv6 or mixed) whose runs span < 2^31 bytes: any gap
 // between slots in the live-piece forms of bounds 1 and 2, at most 64 B in the others (bound 0, and
 // bound 3, which loads a run's first pieces whole); offset/length batches in bounds 1 and 2.
@@ -1288,8 +1278,8 @@ hipError_t launch_pkt_plan(const PktBatchArgs& a, int ip_ver, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_pkt_stream(const PktBatchArgs& a, int ip_ver, int depth, uint32_t spw, bool nt, bool tx, int bound,
-                             hipStream_t s, PktTxRecord* rec, bool scatter) {
+hipError_t launch_pkt_stream(const KernelTune& k, const PktBatchArgs& a, int ip_ver, int depth, uint32_t spw, bool nt, bool tx,
+                             int bound, hipStream_t s, PktTxRecord* rec, bool scatter) {
     if (spw == 0u || spw > kMaxRunPkts || bound < 0 || bound > 3 || !pkt_stream_supported(a, ip_ver, bound)) {
         return hipErrorInvalidValue;
     }
@@ -1315,8 +1305,8 @@ hipError_t launch_pkt_stream(const PktBatchArgs& a, int ip_ver, int depth, uint3
         if (ip_ver != 0 || rec != nullptr) return hipErrorInvalidValue;
 #define NETCSUM_PS(D_, B_, VL_)                                                                           \
     if (depth == D_ && bound == B_ && vl == VL_)                                                          \
-        return nt ? launch_pkt_stream_t<D_, true, false, 0, B_, VL_, true>(a, spw, s, nullptr, false)     \
-                  : launch_pkt_stream_t<D_, false, false, 0, B_, VL_, true>(a, spw, s, nullptr, false);
+        return nt ? launch_pkt_stream_t<D_, true, false, 0, B_, VL_, true>(k, a, spw, s, nullptr, false)  \
+                  : launch_pkt_stream_t<D_, false, false, 0, B_, VL_, true>(k, a, spw, s, nullptr, false);
         NETCSUM_PS(4, 0, false) NETCSUM_PS(4, 1, false) NETCSUM_PS(4, 2, false) NETCSUM_PS(4, 3, false)
         NETCSUM_PS(8, 0, false) NETCSUM_PS(8, 2, false) NETCSUM_PS(8, 3, false)
         NETCSUM_PS(4, 1, true) NETCSUM_PS(4, 2, true) NETCSUM_PS(8, 2, true)
@@ -1327,7 +1317,7 @@ hipError_t launch_pkt_stream(const PktBatchArgs& a, int ip_ver, int depth, uint3
     // live-piece forms 1 and 2
 #define NETCSUM_P(V_, D_, NT_, TX_, B_, VL_)                                                              \
     if (ip_ver == V_ && depth == D_ && nt == NT_ && tx == TX_ && bound == B_ && vl == VL_)                 \
-        return launch_pkt_stream_t<D_, NT_, TX_, V_, B_, VL_>(a, spw, s, rec, scatter);
+        return launch_pkt_stream_t<D_, NT_, TX_, V_, B_, VL_>(k, a, spw, s, rec, scatter);
 #define NETCSUM_PB(V_, D_, B_, VL_)                                                                       \
     NETCSUM_P(V_, D_, true, false, B_, VL_) NETCSUM_P(V_, D_, false, false, B_, VL_)                      \
     NETCSUM_P(V_, D_, true, true, B_, VL_) NETCSUM_P(V_, D_, false, true, B_, VL_)

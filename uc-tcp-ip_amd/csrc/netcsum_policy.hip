@@ -165,7 +165,7 @@ netcsum::LaunchCfg choose_cfg(const Tune& t, int dev, const netcsum::SegBatchArg
                 // runs of 16 segments for dense batches (C2); varlen ones (C4) size their runs on the
                 // device to about RUN_BYTES (launch_batch), the grid covering the shortest run, or take
                 // runs of 8 (r2ct) with VARLEN_RUN_BYTES 0
-                c.run_bytes = varlen ? netcsum::varlen_run_bytes() : 0u;
+                c.run_bytes = varlen ? netcsum::varlen_run_bytes(t) : 0u;
                 uint64_t run = !varlen ? 16u : c.run_bytes ? netcsum::kVarlenSpwMin : 8u;
                 if (!varlen) {
                     // a run whose bytes are a multiple of 16 KiB (16 x 1 / 2 / 4 / 8 KiB segments) or
@@ -379,7 +379,7 @@ NET_ERR pkt_decide(const Tune& t, const PktJob& j, PktPlan& p) {
     // (NETCSUM_TUNE_STREAM_WAVES set: measurements of fixed residencies take no plans)
     p.plan_ring = !packed && j.bound_pref < 0 && p.d == 4 && !tile_run(tile) &&
                   (tb0 == 4 || (tb0 < 0 && j.n >= 16384u)) && j.rec_only == nullptr &&
-                  !netcsum::stream_waves_tuned() && netcsum::pkt_stream_supported(a, ip_ver, 2);
+                  !netcsum::stream_waves_tuned(t) && netcsum::pkt_stream_supported(a, ip_ver, 2);
     if (p.plan_ring) {
         if (j.off == nullptr && netcsum::pkt_stream_supported(a, ip_ver, 0)) {
             p.run0 = pkt_default_run(ip_ver, per, 20480u);

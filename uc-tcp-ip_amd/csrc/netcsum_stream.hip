@@ -32,7 +32,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
@@ -914,28 +913,28 @@ __global__ void __launch_bounds__(256) seg_live_varlen_kernel(SegBatchArgs A, ui
 }
 
 template <int D, int PH, bool NT, bool CMP>
-hipError_t launch_live_varlen_t(const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
+hipError_t launch_live_varlen_t(const KernelTune& k, const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
     SegBatchArgs a = a0;
-    a.xcd = stream_xcd_mode(1);
+    a.xcd = stream_xcd_mode(k, 1);
     const uint64_t waves = ((uint64_t)a.n_seg + spw - 1u) / spw;
     hipLaunchKernelGGL((seg_live_varlen_kernel<D, PH, NT, CMP>), dim3((unsigned)((waves + 3u) / 4u + (a.plan_out ? 1u : 0u))),
-                       dim3(256), stream_lds_bytes(0), s, a, spw);
+                       dim3(256), stream_lds_bytes(k, 0), s, a, spw);
     return hipGetLastError();
 }
 
 template <int D, int PH, bool NT>
-hipError_t launch_stream_varlen_t(const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
+hipError_t launch_stream_varlen_t(const KernelTune& k, const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
     SegBatchArgs a = a0;
     // r2ct (C4, 1 M packed 40-9000 B): runs of 8, touch, 5 waves per SIMD: 0.680 ms against 0.696 ms
     // for runs of 16 at full residency without the touch. r2zm: the best run is a byte budget, not a
     // count (C4: 3 segments = 13.6 KB, 0.657 ms; 40-1500 B: 32 segments = 25 KB, 0.158 ms against
     // 0.273 for runs of 8), so adaptive runs (run_dev) at full residency are the default.
-    a.touch = stream_touch(true) ? 1u : 0u;
-    a.xcd = stream_xcd_mode(1);
+    a.touch = stream_touch(k, true) ? 1u : 0u;
+    a.xcd = stream_xcd_mode(k, 1);
     const uint64_t waves = ((uint64_t)a.n_seg + spw - 1u) / spw;
     const int grid = (int)((waves + 3u) / 4u);
     hipLaunchKernelGGL((seg_stream_varlen_kernel<D, PH, NT>), dim3(grid), dim3(256),
-                       stream_lds_bytes(a.run_dev != nullptr ? 0 : 5), s, a, spw);
+                       stream_lds_bytes(k, a.run_dev != nullptr ? 0 : 5), s, a, spw);
     return hipGetLastError();
 }
 
@@ -969,17 +968,6 @@ __global__ void __launch_bounds__(1024) varlen_runlen_kernel(const uint64_t* off
 
 }  // namespace
 
-namespace {
-thread_local TuneKnob g_varlen_run_bytes{-1};   // NETCSUM_TUNE_VARLEN_RUN_BYTES: -1 default, 0 fixed runs of 8
-constexpr uint32_t kVarlenRunBytes = 16384u;
-}  // namespace
-
-void set_varlen_run_bytes(int v) { g_varlen_run_bytes.store(v); }
-uint32_t varlen_run_bytes() {
-    const int v = g_varlen_run_bytes.load();
-    return v < 0 ? kVarlenRunBytes : (uint32_t)v;
-}
-
 hipError_t launch_varlen_runlen(const uint64_t* offs, const uint16_t* lens, uint32_t n, uint32_t extra, uint32_t run_bytes,
                                 uint32_t spw_min, uint32_t* out, uint32_t* plan_out, uint32_t tag, hipStream_t s) {
     hipLaunchKernelGGL(varlen_runlen_kernel, dim3(1), dim3(1024), 0, s, offs, lens, n, extra, run_bytes, spw_min, out,
@@ -992,9 +980,9 @@ namespace {
 constexpr uint32_t kXcdChunk = 256u;   // blocks per XCD chunk (xcd_block mode) for strided batches
 
 template <int D, int PH, bool NT, bool ONE>
-hipError_t launch_stream_t(const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
+hipError_t launch_stream_t(const KernelTune& k, const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
     SegBatchArgs a = a0;
-    a.touch = stream_touch(true) ? 1u : 0u;
+    a.touch = stream_touch(k, true) ? 1u : 0u;
     // block order: one slice of the runs per XCD, or — when a slice spans >= 1 GiB — XCD chunks of
     // 256 blocks in turn. One slice per XCD puts the 8 XCDs' streams n/8 strides apart — for C5 2^23 x
     // 375 B, a multiple of 8 MiB — and on boxes where the shard's pages land that way the streams
@@ -1003,14 +991,14 @@ hipError_t launch_stream_t(const SegBatchArgs& a0, uint32_t spw, hipStream_t s) 
     // Elsewhere chunks cost 0.2-0.4 % (C5 3.517 / 3.522 against 3.507 / 3.513; C2 0.2189 against 0.2180,
     // r6n, r6q_runs.log), and C2's 200-MB slices never collided (r6e-r6p), so they keep the slices.
     const uint64_t span = (uint64_t)a.n_seg * (a.seg_stride ? a.seg_stride : a.seg_len);
-    a.xcd = stream_xcd_mode(span / 8u >= (1ull << 30) ? kXcdChunk : 1u);
-    a.gather = store_gather() ? 1u : 0u;
+    a.xcd = stream_xcd_mode(k, span / 8u >= (1ull << 30) ? kXcdChunk : 1u);
+    a.gather = store_gather(k) ? 1u : 0u;
     const uint64_t waves = ((uint64_t)a.n_seg + spw - 1u) / spw;
     const int grid = (int)((waves + 3u) / 4u);
     // dense batches default to 5 waves per SIMD with the row touch: C2 0.2188 ms against 0.2346 ms
     // without either (r2ct; 0.2268 touch only, 0.2300 cap only); the residency cap's LDS reservation
     // less the kernel's static LDS (the results' gather), so that the same number of blocks fit
-    const uint32_t lds = stream_lds_bytes(ONE ? 5 : 0);
+    const uint32_t lds = stream_lds_bytes(k, ONE ? 5 : 0);
     const uint32_t kStatic = kGatherMax * 2u + 16u;
     hipLaunchKernelGGL((seg_stream_kernel<D, PH, NT, ONE>), dim3(grid), dim3(256), lds > kStatic ? lds - kStatic : lds,
                        s, a, spw);
@@ -1083,79 +1071,20 @@ __global__ void __launch_bounds__(256) read_run_kernel(const uint8_t* base, uint
     }
 }
 
-thread_local TuneKnob g_live_compact{-1};   // NETCSUM_TUNE_LIVE_COMPACT
-thread_local TuneKnob g_store_gather{-1};   // NETCSUM_TUNE_STORE_GATHER
-thread_local TuneKnob g_stream_waves{-1};
-thread_local TuneKnob g_stream_touch{-1};
-thread_local TuneKnob g_stream_xcd{-1};
-}
+}  // namespace
 
-hipError_t launch_read_run(const void* d_p, uint64_t n_bytes, unsigned long long* d_sink, hipStream_t s, bool sleep) {
+hipError_t launch_read_run(const KernelTune& k, const void* d_p, uint64_t n_bytes, unsigned long long* d_sink, hipStream_t s,
+                           bool sleep) {
     const uint64_t waves = (n_bytes + kProbeRun - 1u) / kProbeRun;
-    const uint32_t xcd = stream_xcd_mode(0);
+    const uint32_t xcd = stream_xcd_mode(k, 0);
     if (sleep) {
-        hipLaunchKernelGGL(read_run_kernel<2>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(5), s,
+        hipLaunchKernelGGL(read_run_kernel<2>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(k, 5), s,
                            static_cast<const uint8_t*>(d_p), n_bytes, d_sink, xcd);
     } else {
-        hipLaunchKernelGGL(read_run_kernel<0>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(5), s,
+        hipLaunchKernelGGL(read_run_kernel<0>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(k, 5), s,
                            static_cast<const uint8_t*>(d_p), n_bytes, d_sink, xcd);
     }
     return hipGetLastError();
-}
-
-void set_store_gather(int v) {
-    g_store_gather.store(v);
-}
-
-bool store_gather() {
-    return g_store_gather.load() != 0;
-}
-
-void set_live_compact(int v) {
-    g_live_compact.store(v);
-}
-
-bool live_compact() {
-    return g_live_compact.load() != 0;
-}
-
-void set_stream_waves(int w) {
-    g_stream_waves.store(w);
-}
-
-bool stream_waves_tuned() {
-    return g_stream_waves.load(std::memory_order_relaxed) >= 0;
-}
-
-uint32_t stream_lds_bytes(int auto_waves) {
-    const int g = g_stream_waves.load(std::memory_order_relaxed);
-    const int w = g >= 0 ? g : auto_waves;
-    // w workgroups of 4 waves per CU = w waves per SIMD: the largest 512-B multiple of which w fit
-    // the 160 KiB of LDS and w + 1 do not
-    return (w >= 3 && w <= 8) ? ((163840u / (uint32_t)w) & ~511u) : 0u;
-}
-
-void set_stream_touch(int t) {
-    g_stream_touch.store(t);
-}
-
-void set_stream_xcd(int on) {
-    g_stream_xcd.store(on);
-}
-
-bool stream_xcd(bool auto_on) {
-    const int x = g_stream_xcd.load(std::memory_order_relaxed);
-    return x < 0 ? auto_on : x != 0;
-}
-
-uint32_t stream_xcd_mode(uint32_t auto_mode) {
-    const int x = g_stream_xcd.load(std::memory_order_relaxed);
-    return x < 0 ? auto_mode : (uint32_t)x;
-}
-
-bool stream_touch(bool auto_on) {
-    const int t = g_stream_touch.load(std::memory_order_relaxed);
-    return t < 0 ? auto_on : t != 0;
 }
 
 // Packed segments of >= 1 KiB (stride == len): the form the library picks by default (C2, C5).
@@ -1166,11 +1095,11 @@ bool stream_dense(const SegBatchArgs& a) {
 namespace {
 
 template <int D>
-hipError_t launch_stream_d(const SegBatchArgs& a, uint32_t spw, bool nt, hipStream_t s) {
+hipError_t launch_stream_d(const KernelTune& k, const SegBatchArgs& a, uint32_t spw, bool nt, hipStream_t s) {
     const int ph = stream_ph(a);
     const bool one = stream_one(a);
 #define NETCSUM_L(PH_, NT_, ONE_) \
-    if (ph == PH_ && nt == NT_ && one == ONE_) return launch_stream_t<D, PH_, NT_, ONE_>(a, spw, s);
+    if (ph == PH_ && nt == NT_ && one == ONE_) return launch_stream_t<D, PH_, NT_, ONE_>(k, a, spw, s);
 #define NETCSUM_L2(PH_) NETCSUM_L(PH_, true, true) NETCSUM_L(PH_, true, false) NETCSUM_L(PH_, false, true) \
     NETCSUM_L(PH_, false, false)
     NETCSUM_L2(0) NETCSUM_L2(1) NETCSUM_L2(2)
@@ -1223,12 +1152,12 @@ int stream_occupancy(int depth, const SegBatchArgs& a, bool nt) {
     return (e == hipSuccess && occ > 0) ? occ : 1;
 }
 
-hipError_t launch_stream_batch(const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
+hipError_t launch_stream_batch(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
     if (spw == 0u || spw > kMaxRun) return hipErrorInvalidValue;
     if (a.seg_off != nullptr) {                       // varlen: depth 4 or 8
         const int ph = stream_ph(a);
 #define NETCSUM_V(D_, PH_, NT_) \
-        if ((depth == 8) == (D_ == 8) && ph == PH_ && nt == NT_) return launch_stream_varlen_t<D_, PH_, NT_>(a, spw, s);
+        if ((depth == 8) == (D_ == 8) && ph == PH_ && nt == NT_) return launch_stream_varlen_t<D_, PH_, NT_>(k, a, spw, s);
         NETCSUM_V(4, 0, true) NETCSUM_V(4, 0, false) NETCSUM_V(4, 1, true) NETCSUM_V(4, 1, false)
         NETCSUM_V(4, 2, true) NETCSUM_V(4, 2, false) NETCSUM_V(8, 0, true) NETCSUM_V(8, 0, false)
         NETCSUM_V(8, 1, true) NETCSUM_V(8, 1, false) NETCSUM_V(8, 2, true) NETCSUM_V(8, 2, false)
@@ -1236,30 +1165,30 @@ hipError_t launch_stream_batch(const SegBatchArgs& a, int depth, uint32_t spw, b
         return hipErrorInvalidValue;
     }
     switch (depth) {
-    case 4: return launch_stream_d<4>(a, spw, nt, s);
-    case 6: return launch_stream_d<6>(a, spw, nt, s);
-    case 8: return launch_stream_d<8>(a, spw, nt, s);
+    case 4: return launch_stream_d<4>(k, a, spw, nt, s);
+    case 6: return launch_stream_d<6>(k, a, spw, nt, s);
+    case 8: return launch_stream_d<8>(k, a, spw, nt, s);
     default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_live_varlen(const SegBatchArgs& a, int depth, uint32_t spw, hipStream_t s) {
+hipError_t launch_live_varlen(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, hipStream_t s) {
     if (a.seg_off == nullptr || spw == 0u || spw > 64u) return hipErrorInvalidValue;
     // PH 2 loads 5 aligned 16-B chunks of each pseudo-header: <= 64 B from any start (stream_supported's
     // limit, checked here too so that no caller can reach the kernel with a longer one)
     if (a.pseudo != nullptr && a.pseudo_len > 64u) return hipErrorInvalidValue;
     const int ph = stream_ph(a);
-    const bool cmp = live_compact();
+    const bool cmp = live_compact(k);
 #define NETCSUM_LV(D_, PH_) \
-    if (depth == D_ && ph == PH_) return cmp ? launch_live_varlen_t<D_, PH_, true, true>(a, spw, s) \
-                                             : launch_live_varlen_t<D_, PH_, true, false>(a, spw, s);
+    if (depth == D_ && ph == PH_) return cmp ? launch_live_varlen_t<D_, PH_, true, true>(k, a, spw, s) \
+                                             : launch_live_varlen_t<D_, PH_, true, false>(k, a, spw, s);
     NETCSUM_LV(4, 0) NETCSUM_LV(4, 1) NETCSUM_LV(4, 2) NETCSUM_LV(8, 0) NETCSUM_LV(8, 1) NETCSUM_LV(8, 2)
 #undef NETCSUM_LV
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_chain_live_records(const ChainBatchArgs& c, uint32_t* rec, uint32_t cap, int depth, uint32_t spw, bool cmp,
-                                     hipStream_t s) {
+hipError_t launch_chain_live_records(const KernelTune& k, const ChainBatchArgs& c, uint32_t* rec, uint32_t cap, int depth,
+                                     uint32_t spw, bool cmp, hipStream_t s) {
     if (rec == nullptr || spw == 0u || spw > 64u || cap == 0u) return hipErrorInvalidValue;
     SegBatchArgs a{};
     a.base = c.base;
@@ -1268,12 +1197,12 @@ hipError_t launch_chain_live_records(const ChainBatchArgs& c, uint32_t* rec, uin
     a.n_seg = cap;                                             // capacity; the count is chain_first[n]
     a.n_dev = c.first + c.n;
     a.out = rec;
-    a.xcd = stream_xcd_mode(1);
+    a.xcd = stream_xcd_mode(k, 1);
     const dim3 grid((unsigned)((((uint64_t)cap + spw - 1u) / spw + 3u) / 4u));
 #define NETCSUM_LC(D_)                                                                                         \
     if (depth == D_) {                                                                                         \
-        if (cmp) hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, true, true>), grid, dim3(256), stream_lds_bytes(0), s, a, spw); \
-        else hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, false, true>), grid, dim3(256), stream_lds_bytes(0), s, a, spw); \
+        if (cmp) hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, true, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw); \
+        else hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, false, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw); \
         return hipGetLastError();                                                                              \
     }
     NETCSUM_LC(4) NETCSUM_LC(8)
