@@ -466,6 +466,18 @@ NET_ERR  NetUtil_MI355X_FragSumVerify      (const NETCSUM_FRAG_SUM *frag,
  * is the driver's matter: the reference's own 802.3 length check assumes it does (:2268), and the rule
  * restates that check unchanged. The FCS is not verified.
  *
+ * The classes are pinned to the reference's own IF/net_if_802x.c (tests/golden/reference_ether_vectors.json:
+ * what the untouched NetIF_802x_Rx did with each test frame, built with IPv4 + IPv6, with the template's
+ * IPv4 + IGMP, and with IPv4 and multicast off). Two things are the stack's configuration (Source/
+ * net_cfg_net.h) and not this call's:
+ *   - An IPv4-only stack must treat the *_IPV6 classes as its invalid-type discard: without IPv6 the
+ *     reference has no case for type 0x86DD and rejects the frame with NET_IF_ERR_INVALID_ETHER_TYPE /
+ *     NET_IF_ERR_INVALID_SNAP_TYPE (RxInvFrameCtr). This call classifies by the frame alone and returns
+ *     ETHER_IPV6 / SNAP_IPV6 whatever the stack was built with.
+ *   - eth_cfg without NETCSUM_ETHCFG_MCAST_RX corresponds to no IPv6-enabled reference build: IPv6 on an
+ *     Ethernet interface enables MLDP and with it NET_MCAST_RX_MODULE_EN. Only an IPv4 stack with
+ *     NET_MCAST_CFG_IPv4_RX_EN disabled rejects group destinations.
+ *
  * Rules, in the reference's order; the first check that fails names the class:
  *   1. len < 60 (NET_IF_802x_FRAME_MIN_SIZE): INV_FRAME_SIZE, from len alone — no octet of the frame
  *      is read.

@@ -44,6 +44,9 @@ typedef void (*CPU_FNCT_PTR)(void *);
 #define CPU_ENDIAN_TYPE_LITTLE    2
 #define CPU_CFG_ENDIAN_TYPE       CPU_ENDIAN_TYPE_LITTLE
 
+/* the stack asks for a core version of at least 1.30; net.h checks it with only this header included */
+#define CPU_CORE_VERSION          13000u
+
 /* critical sections: one thread, nothing to mask */
 #define CPU_SR_ALLOC()
 #define CPU_CRITICAL_ENTER()      do { } while (0)

@@ -1,12 +1,10 @@
-/* Stand-in for the CPU core services header (see cpu.h here). The stack asks for a core version
- * of at least 1.30 and, with 32-bit timestamps disabled, uses only the type names below. */
+/* Stand-in for the CPU core services header (see cpu.h here). With 32-bit timestamps disabled the
+ * stack uses only the type names below (the core version it asks for is in cpu.h). */
 #ifndef NETCSUM_REF_CPU_CORE_H
 #define NETCSUM_REF_CPU_CORE_H
 
 #include <cpu.h>
 #include <lib_def.h>
-
-#define CPU_CORE_VERSION     13000u
 
 typedef int         CPU_ERR;
 #define CPU_ERR_NONE         0

@@ -42,6 +42,8 @@
 #define DEF_BIT_05                DEF_BIT(5)
 #define DEF_BIT_06                DEF_BIT(6)
 #define DEF_BIT_07                DEF_BIT(7)
+#define DEF_BIT_12                DEF_BIT(12)
+#define DEF_BIT_13                DEF_BIT(13)
 #define DEF_BIT_SET(val, mask)    ((val) |= (mask))
 #define DEF_BIT_CLR(val, mask)    ((val) &= ~(mask))
 #define DEF_BIT_IS_SET(val, mask) (((mask) != 0u && ((val) & (mask)) == (mask)) ? DEF_YES : DEF_NO)
@@ -51,5 +53,8 @@
 #define DEF_CHK_VAL_MIN(val, lo)  (((val) < (lo)) ? DEF_FAIL : DEF_OK)
 #define DEF_CHK_VAL_MAX(val, hi)  (((val) > (hi)) ? DEF_FAIL : DEF_OK)
 #define DEF_CHK_VAL(val, lo, hi)  ((((val) < (lo)) || ((val) > (hi))) ? DEF_FAIL : DEF_OK)
+
+#define DEF_MIN(a, b)             (((a) < (b)) ? (a) : (b))
+#define DEF_MAX(a, b)             (((a) > (b)) ? (a) : (b))
 
 #endif
