@@ -304,8 +304,27 @@ NET_ERR  NetUtil_MI355X_TxFinalizeIP       (void            *d_base,
  *   flags do not remove, reject it. Decisions therefore equal the reference's with the flags off:
  *   a frame is delivered iff its checksums pass (or it carries none), and every frame the
  *   reference drops at a checksum check is dropped. The DROP code names the counter the reference
- *   increments at that check; for a frame that ALSO fails an earlier non-checksum check (an
- *   ICMPv4 type/code/length, net_icmpv4.c:1500-1659) the reference counts that check instead.
+ *   increments at that check; for a frame that ALSO fails a non-checksum check the reference makes
+ *   BEFORE that checksum, the reference counts that check instead (both sides drop, the counter
+ *   differs). Those checks, in the reference's own order (recorded from its compiled code,
+ *   tests/golden/reference_ip_vectors.json; the table is PRECEDING in tests/test_ip_reference_cpu.py):
+ *     every transport DROP   after the header checksum, NetIPv4_RxPktValidate goes on to the reserved
+ *                            flag (RxInvFlagsCtr), the destination (RxDestCtr, RxDestBcastCtr), the source
+ *                            (RxInvAddrSrcCtr) and the options (RxInvOptsCtr), net_ipv4.c:5258-5800 (its
+ *                            fragment-field and protocol checks meet no transport DROP: such datagrams
+ *                            are L4_UNVERIFIED or carry no verdict); nothing precedes the IPv4 header
+ *                            checksum itself but version, header length and total length: MALFORMED here
+ *     TCP                    ports (RxHdrPortSrcCtr, RxHdrPortDestCtr), header and segment length
+ *                            (RxHdrLenCtr, RxHdrSegLenCtr), flags (RxHdrFlagsCtr)
+ *     UDP                    ports (RxHdrPortSrcCtr, RxHdrPortDestCtr); the datagram length
+ *                            (RxHdrDatagramLenCtr) is L4_MALFORMED here: no verdict, delivered
+ *     ICMPv4                 broadcast / multicast destination (RxBcastCtr, RxMcastCtr), type, code,
+ *                            length, parameter pointer (RxInvTypeCtr, RxInvCodeCtr, RxInvMsgLenCtr,
+ *                            RxInvPtrCtr), net_icmpv4.c:1480-1659
+ *     IGMP                   length, version, destination, type (RxHdrMsgLenCtr, RxHdrVerCtr,
+ *                            RxPktInvalidAddrDestCtr, RxHdrTypeCtr): the reference speaks IGMPv1 only
+ *   A datagram whose version nibble is 6 is judged as IPv6 (mixed bursts); behind an IPv4 frame type the
+ *   reference counts IPv4.RxInvVerCtr.
  *   IPv4 fragments: the transport checksum covers the reassembled datagram (net_ipv4.c:6523), which
  *   a per-frame burst does not hold; they are verified at the IP header only (DELIVER_L4_UNVERIFIED,
  *   what any offloading NIC does). RxBurstSums ((2b''') below) also reports each fragment's payload

@@ -7,7 +7,8 @@ sites call them (never used by the product):
                                                                     net_tcp.c:7851-7857
       UDP         field 0 -> no checksum (accepted); else DataVerify(NET_BUF{UDP_V4}, pseudo{..,17,len})
                                                                     net_udp.c:1893-1934
-      ICMP        DataVerify(NET_BUF{ICMP_V4, ICMP_MsgIx = IHL*4}, NULL, 0)    net_icmpv4.c:1676
+      ICMP        echo request / reply: DataVerify(NET_BUF{ICMP_V4, ICMP_MsgIx = IHL*4}, NULL, 0)
+                  every other type: HdrVerify(icmp_hdr, msg len)    net_icmpv4.c:1661-1689
       IGMP        HdrVerify(igmp_hdr, msg len)                      net_igmp.c:1332
   Tx  the same sums through the Calc functions with the checksum fields zeroed first, written back
       as the host-order value (net_ipv4.c:9573-9586, net_tcp.c:29824-29862, net_udp.c:2891-2937).
@@ -45,24 +46,43 @@ def _l4_chain(pkt: bytes, proto_type: int, hlen: int, l4len: int, icmp=False):
                            "data_len": l4len}])
 
 
-def rx_validate(pkt: bytes) -> int:
+ICMPV4_DATA_VERIFY_TYPES = (0, 8)         # echo reply / request; every other type the reference sums: HdrVerify
+
+
+def rx_validate(pkt: bytes, calls: list | None = None) -> int:
+    """The NETCSUM_PKT_* verdict of one IPv4 datagram. calls (optional) receives one (function, protocol
+    type, offset of the summed part in the datagram, octet count or DataLen, pseudo-header octets, result)
+    per checksum call made, in order: what tests/test_ip_reference_cpu.py holds against the calls the
+    reference's own receive path made."""
     pkt = bytes(pkt)
     p = _parse(pkt)
     if p is None:
         return MALFORMED
     hlen, tot, frag, proto, src, dst = p
     hb = netcsum.HostBytes(pkt)
-    ok, _ = oracle.hdr_verify(hb.ptr, hlen)
-    f = IP_OK if ok else 0
+
+    def note(fn, proto_type, off, ln, pseudo, result):
+        if calls is not None:
+            calls.append((fn, proto_type, off, ln, pseudo, int(bool(result))))
+        return result
+
+    def hdr(off, ln):
+        return note("hdr_verify", 0, off, ln, b"", oracle.hdr_verify(ctypes.addressof(hb.arr) + off, ln)[0])
+
+    def data(proto_type, ln, pseudo=None, icmp=False):
+        ch = _l4_chain(pkt, proto_type, hlen, ln, icmp=icmp)
+        ph = netcsum.HostBytes(pseudo) if pseudo is not None else None
+        v, _ = oracle.data_verify(ch.ptr, ph.ptr if ph else None, len(pseudo) if pseudo is not None else 0)
+        return note("data_verify", proto_type, hlen, ln, pseudo or b"", v)
+
+    f = IP_OK if hdr(0, hlen) else 0
     if frag:
         return f | FRAGMENT
     l4len = tot - hlen
     if proto == 6:
         if l4len < 20:
             return f | L4_MALFORMED
-        ch = _l4_chain(pkt, netcsum.NET_PROTOCOL_TYPE_TCP_V4, hlen, l4len)
-        ph = netcsum.HostBytes(struct.pack("!4s4sBBH", src, dst, 0, 6, l4len))
-        v, err = oracle.data_verify(ch.ptr, ph.ptr, 12)
+        v = data(netcsum.NET_PROTOCOL_TYPE_TCP_V4, l4len, struct.pack("!4s4sBBH", src, dst, 0, 6, l4len))
         return f | L4_CHECKED | (L4_OK if v else 0)
     if proto == 17:
         if l4len < 8:
@@ -72,20 +92,20 @@ def rx_validate(pkt: bytes) -> int:
             return f | L4_MALFORMED
         if pkt[hlen + 6:hlen + 8] == b"\x00\x00":
             return f | UDP_NO_CSUM | L4_OK
-        ch = _l4_chain(pkt, netcsum.NET_PROTOCOL_TYPE_UDP_V4, hlen, udp_len)
-        ph = netcsum.HostBytes(struct.pack("!4s4sBBH", src, dst, 0, 17, udp_len))
-        v, err = oracle.data_verify(ch.ptr, ph.ptr, 12)
+        v = data(netcsum.NET_PROTOCOL_TYPE_UDP_V4, udp_len, struct.pack("!4s4sBBH", src, dst, 0, 17, udp_len))
         return f | L4_CHECKED | (L4_OK if v else 0)
     if proto == 1:
         if l4len < 4:
             return f | L4_MALFORMED
-        ch = _l4_chain(pkt, netcsum.NET_PROTOCOL_TYPE_ICMP_V4, hlen, l4len, icmp=True)
-        v, err = oracle.data_verify(ch.ptr, None, 0)
+        if pkt[hlen] in ICMPV4_DATA_VERIFY_TYPES:
+            v = data(netcsum.NET_PROTOCOL_TYPE_ICMP_V4, l4len, icmp=True)
+        else:
+            v = hdr(hlen, l4len)
         return f | L4_CHECKED | (L4_OK if v else 0)
     if proto == 2:
         if l4len < 4:
             return f | L4_MALFORMED
-        v, err = oracle.hdr_verify(ctypes.addressof(hb.arr) + hlen, l4len)
+        v = hdr(hlen, l4len)
         return f | L4_CHECKED | (L4_OK if v else 0)
     return f
 

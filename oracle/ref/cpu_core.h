@@ -14,6 +14,9 @@ typedef CPU_INT64U  CPU_TS64;
 typedef CPU_TS32    CPU_TS;
 typedef CPU_INT32U  CPU_TS_TMR_FREQ;
 
+/* the stack's "cannot happen" exit (argument checks of the external-call layer): stop the process */
+#define CPU_SW_EXCEPTION(ret) __builtin_trap()
+
 #define CPU_CFG_TS_32_EN     DEF_DISABLED
 #define CPU_CFG_TS_64_EN     DEF_DISABLED
 

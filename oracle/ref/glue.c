@@ -13,6 +13,8 @@ RAND_NBR Math_Rand(void) {
     return Math_RandSeedCur;
 }
 
+RAND_NBR Math_RandSeed(RAND_NBR seed) { return seed * 1103515245u + 12345u; }
+
 KAL_TICK KAL_TickGet(KAL_ERR *p_err) {
     *p_err = KAL_ERR_NONE;
     return 0u;

@@ -9,5 +9,6 @@ typedef CPU_INT32U RAND_NBR;
 extern RAND_NBR Math_RandSeedCur;
 void     Math_RandSetSeed(RAND_NBR seed);
 RAND_NBR Math_Rand(void);
+RAND_NBR Math_RandSeed(RAND_NBR seed);                /* the number that follows `seed` */
 
 #endif

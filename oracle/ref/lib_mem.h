@@ -8,6 +8,7 @@
 #include <lib_def.h>
 
 typedef int         LIB_ERR;
+#define LIB_MEM_ERR_NONE  0
 typedef CPU_INT32U  MEM_POOL_BLK_QTY;
 typedef struct { void *opaque; } MEM_SEG;
 typedef struct { void *opaque; } MEM_POOL;
@@ -34,6 +35,20 @@ typedef struct { void *opaque; } MEM_DYN_POOL;
 #define MEM_VAL_COPY_SWAP_16_(dest, src) do { const CPU_INT08U mem_val_b0_ = ((const CPU_INT08U *)(src))[0]; \
                                               ((CPU_INT08U *)(dest))[0] = ((const CPU_INT08U *)(src))[1]; \
                                               ((CPU_INT08U *)(dest))[1] = mem_val_b0_; } while (0)
+#define MEM_VAL_COPY_SWAP_32_(dest, src) do { CPU_INT08U mem_val_t_[4]; MEM_VAL_COPY(mem_val_t_, src, 4u); \
+                                              ((CPU_INT08U *)(dest))[0] = mem_val_t_[3]; ((CPU_INT08U *)(dest))[1] = mem_val_t_[2]; \
+                                              ((CPU_INT08U *)(dest))[2] = mem_val_t_[1]; ((CPU_INT08U *)(dest))[3] = mem_val_t_[0]; } while (0)
+#define MEM_VAL_COPY_16(dest, src)             MEM_VAL_COPY(dest, src, 2u)
+#define MEM_VAL_COPY_32(dest, src)             MEM_VAL_COPY(dest, src, 4u)
+#define MEM_VAL_COPY_SET_INT32U(dest, src)     MEM_VAL_COPY(dest, src, 4u)     /* host order: little-endian */
+#define MEM_VAL_COPY_GET_INT32U_BIG(dest, src) MEM_VAL_COPY_SWAP_32_(dest, src)
+#define MEM_VAL_COPY_SET_INT32U_BIG(dest, src) MEM_VAL_COPY_SWAP_32_(dest, src)
+#define MEM_VAL_SET_INT16U_BIG(addr, val)      do { ((CPU_INT08U *)(addr))[0] = (CPU_INT08U)((CPU_INT16U)(val) >> 8); \
+                                                    ((CPU_INT08U *)(addr))[1] = (CPU_INT08U)(val); } while (0)
+#define MEM_VAL_SET_INT32U_BIG(addr, val)      do { ((CPU_INT08U *)(addr))[0] = (CPU_INT08U)((CPU_INT32U)(val) >> 24); \
+                                                    ((CPU_INT08U *)(addr))[1] = (CPU_INT08U)((CPU_INT32U)(val) >> 16); \
+                                                    ((CPU_INT08U *)(addr))[2] = (CPU_INT08U)((CPU_INT32U)(val) >> 8); \
+                                                    ((CPU_INT08U *)(addr))[3] = (CPU_INT08U)(val); } while (0)
 #define MEM_VAL_COPY_GET_INT16U_BIG(dest, src) MEM_VAL_COPY_SWAP_16_(dest, src)
 #define MEM_VAL_COPY_SET_INT16U_BIG(dest, src) MEM_VAL_COPY_SWAP_16_(dest, src)
 
