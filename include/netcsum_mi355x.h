@@ -533,7 +533,9 @@ NET_ERR  NetUtil_MI355X_FragSumVerify      (const NETCSUM_FRAG_SUM *frag,
  * NET_ERR_FAULT_NULL_PTR; unknown rx_cfg or eth_cfg bits NET_UTIL_ERR_MI355X_INVALID_ARG; n_frame == 0
  * succeeds without a launch. hw_addr is HOST memory (6 octets, or NULL).
  *
- * RxBurstEtherHost ((2e) below): the same from host memory, always by the copy pipeline.
+ * RxBurstEtherHost ((2e) below): the same from host memory. A burst of <= 4096 frames with n_chunks 0
+ * from ONE pinned allocation is served in place by the resident burst server, whose waves do the demux
+ * themselves; every other call takes the copy pipeline. The results are the same bytes either way.
  * EtherClass / RxBurstEtherTally: host logic, no device work. EtherClass is the rules on one frame in
  * host memory (*p_hdr_len, optional: 14 / 22, 0 for the INV_* classes); the tally's rules are
  * RxBurstTally's: ctr[c] += frames of class c; NULL with n_frame != 0 NET_ERR_FAULT_NULL_PTR, a class
@@ -661,9 +663,18 @@ NET_ERR  NetUtil_MI355X_RxBurstSumsHost    (const void      *h_base,
                                             uint32_t         n_chunks);
 
 /* RxBurstEther ((2b'''') above) over frames in host memory — the receive ring itself, h_len the
- * received lengths; h_off == NULL with h_len != NULL is allowed as there. Always the copy pipeline: per
- * chunk the frames' span and descriptors go H2D, then the demux, the packet batch, and action, flags
- * (optional) and l2 come back D2H. */
+ * received lengths; h_off == NULL with h_len != NULL is allowed as there.
+ * In place: with n_chunks 0, n_frame <= 4096, the frames' span (the lowest start to the highest start +
+ * length, from h_off / h_len / stride / frame_len) inside ONE pinned allocation of <= 64 MiB, and
+ * NETCSUM_TUNE_BURST_ZERO_COPY 3 (the default), the burst is posted to the resident burst server as
+ * the packet bursts above are: the wave that owns a run of frames classifies them and streams their
+ * datagrams, and action, flags and l2 arrive in coherent pinned memory the call polls.
+ * NetUtil_MI355X_LastLaunch() then reads "ether_demux b=<server blocks> | burst_server_kernel rx
+ * form=ether pkts_per_wave=<K> zero-copy".
+ * Every other call (n_chunks != 0, more frames, a pageable ring or one spanning allocations,
+ * BURST_ZERO_COPY 0, 1 or 2) takes the copy pipeline: per chunk the frames' span and descriptors go H2D,
+ * then the demux, the packet batch, and action, flags (optional) and l2 come back D2H. Checks, their
+ * order, error codes and results do not depend on the path. */
 NET_ERR  NetUtil_MI355X_RxBurstEtherHost   (const void      *h_base,
                                             const uint64_t  *h_off,
                                             const uint16_t  *h_len,

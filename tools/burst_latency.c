@@ -13,7 +13,14 @@
  *                      and the host polls the results; _auto_copy: the same with
  *                      NETCSUM_TUNE_BURST_ZERO_COPY 0, the copy pipeline; _launch: 2, a kernel launch
  *                      per burst; from 1024 frames also in 2-16 chunks: _cK)
- * and a check that every Rx action is DELIVER. One JSON line per n on stdout.
+ *   rx_ether_host_auto RxBurstEtherHost with n_chunks 0 on the same pinned ring from +0: the slots hold
+ *                      Ethernet II frames of 1514 octets (a fixed unicast destination and source in
+ *                      front of the type), passed with a received-length array and no interface
+ *                      address; up to 4096 frames the resident burst server demuxes and checks them in
+ *                      place (_auto_copy: the same call under NETCSUM_TUNE_BURST_ZERO_COPY 0, the copy
+ *                      pipeline)
+ * and a check that every Rx action is DELIVER and every frame's class ETHER_IPV4. One JSON line per n on
+ * stdout.
  *
  * Built here (the binary travels with the tree; tools/build/ is git-ignored), run on the GPU box:
  *   gcc -O2 -std=c11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tools/burst_latency.c \
@@ -35,6 +42,7 @@
 #define SLOT   1520u
 #define IP_AT  14u
 #define DGRAM  1500u
+#define FRAME  (IP_AT + DGRAM)
 #define NMAX   262144u
 #define REPS   300
 #define WARM   20
@@ -89,7 +97,9 @@ static void build(uint8_t *slot)
 {
     uint8_t *ip = slot + IP_AT, *tcp = ip + 20;
     uint32_t i;
+    static const uint8_t addrs[12] = {0x02, 0xA1, 0xB2, 0xC3, 0xD4, 0xE5, 0x02, 0x50, 0x60, 0x70, 0x80, 0xA0};
     for (i = 0; i < SLOT; ++i) slot[i] = rnd8();
+    memcpy(slot, addrs, sizeof addrs);                          /* destination, source */
     slot[12] = 0x08;
     slot[13] = 0x00;
     ip[0] = 0x45;
@@ -105,9 +115,10 @@ static void build(uint8_t *slot)
     tcp[16] = tcp[17] = 0;
 }
 
-typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST } kind_t;
+typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST, RX_ETHER_HOST } kind_t;
 
-static uint8_t *g_dring, *g_hring, *g_dact, *g_hact;
+static uint8_t *g_dring, *g_hring, *g_dact, *g_hact, *g_hl2;
+static uint16_t *g_hlen;                                        /* received lengths: FRAME each */
 static hipStream_t g_st;
 
 static uint32_t g_chunks;
@@ -129,6 +140,9 @@ static void call(kind_t k, uint32_t n)
         break;
     case TX_HOST:
         NET_OK(NetUtil_MI355X_TxBurstHost(g_hring + IP_AT, NULL, NULL, SLOT, DGRAM, n, NULL, chunks));
+        break;
+    case RX_ETHER_HOST:
+        NET_OK(NetUtil_MI355X_RxBurstEtherHost(g_hring, NULL, g_hlen, SLOT, 0, n, 0u, 0u, NULL, g_hact, NULL, g_hl2, chunks));
         break;
     }
 }
@@ -214,6 +228,10 @@ int main(int argc, char **argv)
     HIP_OK(hipMalloc((void **)&g_dact, NMAX));
     HIP_OK(hipHostMalloc((void **)&g_hring, bytes, 0));
     HIP_OK(hipHostMalloc((void **)&g_hact, NMAX, 0));
+    HIP_OK(hipHostMalloc((void **)&g_hl2, NMAX, 0));
+    g_hlen = malloc(NMAX * sizeof *g_hlen);
+    if (g_hlen == NULL) return 2;
+    for (i = 0; i < NMAX; ++i) g_hlen[i] = FRAME;
     for (i = 0; i < NMAX; ++i) build(g_hring + (size_t)i * SLOT);
     NET_OK(NetUtil_MI355X_TxBurstHost(g_hring + IP_AT, NULL, NULL, SLOT, DGRAM, NMAX, NULL, 8u));   /* valid sums */
     HIP_OK(hipMemcpy(g_dring, g_hring, bytes, hipMemcpyHostToDevice));
@@ -221,7 +239,7 @@ int main(int argc, char **argv)
     for (s = 0; s < sizeof sizes / sizeof sizes[0]; ++s) {
         const uint32_t n = sizes[s];
         double rx_dev, tx_dev, rx_host, tx_host;
-        int ok = 1;
+        int ok = 1, z;
         HIP_OK(hipMemset(g_dact, 0xEE, NMAX));
         memset(g_hact, 0xEE, NMAX);
         g_chunks = 1u;
@@ -256,6 +274,16 @@ int main(int argc, char **argv)
             printf(", \"rx_host_us_c%u\": %.2f", g_chunks, time_us(RX_HOST, n));
             printf(", \"tx_host_us_c%u\": %.2f", g_chunks, time_us(TX_HOST, n));
         }
+        /* whole frames from +0 of the same slots (n_chunks 0), and the same under TUNE_BURST_ZERO_COPY 0 */
+        g_chunks = 0u;
+        for (z = 0; z < 2; ++z) {
+            NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, z ? 0 : 3));
+            memset(g_hact, 0xEE, n);
+            memset(g_hl2, 0xEE, n);
+            printf(", \"rx_ether_host_auto%s_us\": %.2f", z ? "_copy" : "", time_us(RX_ETHER_HOST, n));
+            for (i = 0; i < n; ++i) ok &= g_hact[i] == NETCSUM_RX_DELIVER && g_hl2[i] == NETCSUM_L2_ETHER_IPV4;
+        }
+        NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, 3));
         printf(", \"all_delivered_auto\": %s}\n", ok ? "true" : "false");
         fflush(stdout);
         if (!ok) return 1;
@@ -265,6 +293,8 @@ int main(int argc, char **argv)
     HIP_OK(hipFree(g_dact));
     HIP_OK(hipHostFree(g_hring));
     HIP_OK(hipHostFree(g_hact));
+    HIP_OK(hipHostFree(g_hl2));
+    free(g_hlen);
     HIP_OK(hipStreamDestroy(g_st));
     return 0;
 }

@@ -4,6 +4,9 @@
 // NetIF_802x_Rx / NetIF_802x_RxPktFrameDemux, in their order of checks) and writes the class and the
 // offset/length descriptor of the IP datagram for the offset/length Rx burst that follows on the stream.
 //
+// (The resident burst server does the same step inside the waves that stream the datagrams, without this
+// pass: netcsum_pktstream.hip pkt_ether_run. The head load is stated once for both, netcsum_etherhead.h.)
+//
 // Reads: the rules need a frame's first 23 octets. A frame may start at any address, so the lane loads
 // the aligned dwords that cover [start, start + 23) — six, or seven when the start is 2 or 3 past a
 // dword — and shifts them into place (v_alignbyte_b32); no byte loads (the compiler fetches the same
@@ -16,36 +19,22 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/netcsum_ether.h"
+#include "netcsum_etherhead.h"
 #include "netcsum_kernels.h"
 
 namespace netcsum {
 
 namespace {
 
-typedef const __attribute__((address_space(1))) uint32_t gu32;
-
 __global__ __launch_bounds__(kEtherDemuxBlock) void ether_demux_kernel(const EtherDemuxArgs A) {
     const uint32_t i = blockIdx.x * kEtherDemuxBlock + threadIdx.x;
     if (i >= A.n) return;
     const uint64_t o = A.off ? A.off[i] : (uint64_t)i * A.stride;
     const uint32_t len = A.len ? A.len[i] : A.len_u;
-    uint32_t w[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    if (len >= NETCSUM_L2_FRAME_MIN) {
-        const uintptr_t start = reinterpret_cast<uintptr_t>(A.base) + o;
-        const uint32_t sh = (uint32_t)(start & 3u);
-        gu32* q = reinterpret_cast<gu32*>(start - sh);
-        uint32_t d[7];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) d[k] = q[k];
-        d[6] = sh >= 2u ? q[6] : 0u;                     // octets 20-22 end in dword 6 only then
-#pragma unroll
-        for (int k = 0; k < 6; ++k) w[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
-    }
-    const uint32_t cls = NetCsum_L2Class(len, w, A.eth_cfg, (int)A.have_hw, A.hw_lo, A.hw_hi);
-    const uint32_t ip = NetCsum_L2IPOctets(cls, len, w);
-    A.l2_out[i] = (uint8_t)cls;
-    A.off_out[i] = ip ? o + NetCsum_L2HdrLen(cls) : o;
-    A.len_out[i] = (uint16_t)ip;
+    const EtherHead h = ether_head(reinterpret_cast<uintptr_t>(A.base) + o, len, A.eth_cfg, A.have_hw, A.hw_lo, A.hw_hi);
+    A.l2_out[i] = (uint8_t)h.cls;
+    A.off_out[i] = h.ip ? o + NetCsum_L2HdrLen(h.cls) : o;
+    A.len_out[i] = (uint16_t)h.ip;
 }
 
 }  // namespace

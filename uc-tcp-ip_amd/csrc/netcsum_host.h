@@ -132,5 +132,7 @@ constexpr int kServerBlocks = 16;
 // The resident burst server's form for a burst (BurstPost::form >> 1 and its run length), or false
 // when the burst is outside the run-stream kernel's domain (the launch path takes it).
 bool server_form(const uint64_t* h_off, uint64_t stride, CPU_INT16U pkt_len, uint32_t n_pkt, uint32_t* form, uint32_t* spw);
+// Its run length for the offset/length form, which the Ether form (BurstPost::form kBurstEther) shares.
+uint32_t server_run(uint32_t n_pkt);
 
 }  // namespace nchost

@@ -456,7 +456,8 @@ constexpr int kBurstBound = 0;
 constexpr uint64_t kBurstZCSpan = 64ull << 20;          // ring bytes the kernel may read in place
 constexpr size_t kBurstWord = 0, kBurstPost = 64, kBurstClosed = 128, kBurstFlags = 256, kBurstAct = kBurstFlags + kBurstZC,
                  kBurstOff = kBurstAct + kBurstZC, kBurstLen = kBurstOff + 8u * kBurstZC,
-                 kBurstRec = kBurstLen + 2u * kBurstZC, kBurstHostBytes = kBurstRec + 8u * kBurstZC;
+                 kBurstRec = kBurstLen + 2u * kBurstZC, kBurstL2 = kBurstRec + 8u * kBurstZC,
+                 kBurstHostBytes = kBurstL2 + kBurstZC;
 // device side: [flags | actions | Tx records]
 constexpr size_t kBurstDevRec = 2u * kBurstZC, kBurstDevBytes = kBurstDevRec + 8u * kBurstZC;
 
@@ -522,7 +523,8 @@ static NET_ERR launch_server(const Tune& t, HostCtx& c, uint64_t seq0) {
     a.closed = reinterpret_cast<unsigned long long*>(c.h_burst_dev + kBurstClosed);
     a.flags = c.h_burst_dev + kBurstFlags;
     a.act = c.h_burst_dev + kBurstAct;
-    a.rec = reinterpret_cast<netcsum::PktTxRecord*>(c.h_burst_dev + kBurstRec);
+    a.l2 = c.h_burst_dev + kBurstL2;
+    a.rec =reinterpret_cast<netcsum::PktTxRecord*>(c.h_burst_dev + kBurstRec);
     a.off = reinterpret_cast<const uint64_t*>(c.h_burst_dev + kBurstOff);
     a.len = reinterpret_cast<const uint16_t*>(c.h_burst_dev + kBurstLen);
     a.seq0 = seq0;
@@ -624,10 +626,14 @@ static NET_ERR burst_server_run(const Tune& t, HostCtx& c, netcsum::BurstPost p,
 
 // NetUtil_MI355X_LastLaunch after a zero-copy burst: which path served it (the tests check that the
 // zero-copy path, not the copy pipeline, was taken)
+// (an Ether burst: "ether_demux b=<blocks> | " in front, RxBurstEther's shape, with the server's blocks,
+// whose waves did the demux)
 static void server_launch_name(uint32_t form, uint32_t spw, bool tx) {
-    char d[96];
-    snprintf(d, sizeof d, "burst_server_kernel %s form=%s pkts_per_wave=%u zero-copy", tx ? "tx" : "rx",
-             form == netcsum::kBurstWhole ? "whole" : form == netcsum::kBurstLive ? "live" : "offlen", spw);
+    char d[128];
+    const bool ether = (form & netcsum::kBurstKindMask) == netcsum::kBurstEther;
+    int k = ether ? snprintf(d, sizeof d, "ether_demux b=%d | ", kServerBlocks) : 0;
+    snprintf(d + k, sizeof d - (size_t)k, "burst_server_kernel %s form=%s pkts_per_wave=%u zero-copy", tx ? "tx" : "rx",
+             ether ? "ether" : form == netcsum::kBurstWhole ? "whole" : form == netcsum::kBurstLive ? "live" : "offlen", spw);
     netcsum::set_last_launch(d);
 }
 
@@ -1017,7 +1023,84 @@ NET_ERR NetUtil_MI355X_RxBurstSumsHost(const void* h_base, const uint64_t* h_off
     return pkt_host(h, n_chunks);
 }
 
-// RxBurstEther over frames in host memory: the copy pipeline of pkt_host_copy with the frame-level
+// The octets [lo, hi) from the base that frames s0 .. s0 + ns - 1 of an Ether burst occupy (offsets and
+// received lengths come separately there: a ring of slots has lengths and no offsets).
+static void ether_span(const uint64_t* h_off, const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t s0,
+                       uint32_t ns, uint64_t* lo, uint64_t* hi) {
+    *lo = ~0ull;
+    *hi = 0;
+    for (uint32_t i = s0; i < s0 + ns; ++i) {
+        const uint64_t o = h_off ? h_off[i] : (uint64_t)i * stride;
+        *lo = std::min<uint64_t>(*lo, o);
+        *hi = std::max<uint64_t>(*hi, o + (h_len ? h_len[i] : frame_len));
+    }
+}
+
+// An Ether burst over a pinned ring in place, by the resident server's Ether form (netcsum_pktstream.hip
+// pkt_ether_run: the wave that owns a run classifies its frames and streams their datagrams): the
+// descriptors the burst gives are staged in the context's coherent memory, flags, actions and classes
+// arrive there behind 0xFF sentinels (no class is >= 16), and the host polls all three. Taken under
+// rx_burst_zero_copy's conditions — at most kBurstZC frames whose span is one pinned allocation of at
+// most kBurstZCSpan bytes — and in the server's mode only (TUNE_BURST_ZERO_COPY 3: the launch-per-burst
+// experiments are not extended to frames). *taken = false: the caller takes the copy pipeline.
+static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h_base, const uint64_t* h_off,
+                                        const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t n,
+                                        uint32_t rx_cfg, uint32_t eth_cfg, const uint8_t* hw_addr, uint8_t* h_action,
+                                        uint8_t* h_flags, uint8_t* h_l2, bool* taken) {
+    *taken = false;
+    if (n > kBurstZC) return NET_UTIL_ERR_NONE;
+    uint64_t lo = 0, hi = 0;
+    ether_span(h_off, h_len, stride, frame_len, 0u, n, &lo, &hi);
+    if (hi <= lo || hi - lo > kBurstZCSpan) return NET_UTIL_ERR_NONE;
+    const uint8_t* d_lo = pinned_alias(static_cast<const uint8_t*>(h_base) + lo, hi - lo);
+    if (d_lo == nullptr) return NET_UTIL_ERR_NONE;
+    *taken = true;
+    NET_ERR e = ensure_burst(c);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    uint32_t form = netcsum::kBurstEther;
+    const uint32_t spw = server_run(n);                     // (as the offset/length form)
+    if (h_off) {
+        std::memcpy(c.h_burst + kBurstOff, h_off, (size_t)n * 8u);
+        form |= netcsum::kBurstEtherOff;
+    }
+    if (h_len) {
+        std::memcpy(c.h_burst + kBurstLen, h_len, (size_t)n * 2u);
+        form |= netcsum::kBurstEtherLen;
+    }
+    uint8_t* hf = c.h_burst + kBurstFlags;
+    uint8_t* ha = c.h_burst + kBurstAct;
+    uint8_t* hl = c.h_burst + kBurstL2;
+    std::memset(hf, 0xFF, n);
+    std::memset(ha, 0xFF, n);
+    std::memset(hl, 0xFF, n);
+    netcsum::BurstPost post{};
+    post.ring = reinterpret_cast<uint64_t>(d_lo - lo);      // the base's alias: offsets count from it
+    post.stride = (uint32_t)stride;
+    post.n = n;
+    post.pkt_len = frame_len;
+    post.spw = spw;
+    post.form = form << 1;
+    post.rx_cfg = rx_cfg;
+    post.eth_cfg = eth_cfg;
+    if (hw_addr != nullptr) {
+        post.have_hw = 1u;
+        post.hw_lo = (uint32_t)hw_addr[0] | ((uint32_t)hw_addr[1] << 8) | ((uint32_t)hw_addr[2] << 16) | ((uint32_t)hw_addr[3] << 24);
+        post.hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
+    }
+    server_launch_name(form, spw, false);
+    e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
+                                                              *(volatile const uint8_t*)(ha + i) != 0xFFu &&
+                                                              *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    if (h_flags) std::memcpy(h_flags, hf, n);
+    std::memcpy(h_action, ha, n);
+    std::memcpy(h_l2, hl, n);
+    return NET_UTIL_ERR_NONE;
+}
+
+// RxBurstEther over frames in host memory. A burst from a pinned ring (n_chunks 0, at most 4096 frames in
+// one pinned allocation, TUNE_BURST_ZERO_COPY 3) is served in place by the resident burst server
+// (rx_burst_ether_zero_copy). Every other call: the copy pipeline of pkt_host_copy with the frame-level
 // descriptors (per-frame lengths also without offsets: a ring of slots) and the classes as a third
 // result. Per chunk: H2D of the frames' span and descriptors, the device form (demux, packet batch) on
 // the chunk's stream, D2H of actions, flags and classes.
@@ -1034,18 +1117,19 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
     NET_ERR e = host_ctx(&cp);
     if (e != NET_UTIL_ERR_NONE) return e;
     HostCtx& c = *cp;
+    const Tune& t = tune();
+    if (n_chunks == 0 && t.burst_zc == 3) {                  // a burst from a pinned ring: in place
+        bool taken = false;
+        e = rx_burst_ether_zero_copy(t, c, h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr,
+                                     h_action, h_flags, h_l2, &taken);
+        if (taken) return e;
+    }
     std::vector<HostChunk> ch;
     uint64_t maxb = plan_chunks(nullptr, nullptr, stride, frame_len, n_frame, n_chunks == 0 ? 1u : n_chunks, ch);
-    if (h_off != nullptr || h_len != nullptr) {              // (offsets and received lengths come separately here:
-        maxb = 0;                                            // a ring of slots has lengths and no offsets)
+    if (h_off != nullptr || h_len != nullptr) {
+        maxb = 0;
         for (HostChunk& k : ch) {
-            k.lo = ~0ull;
-            k.hi = 0;
-            for (uint32_t i = k.s0; i < k.s0 + k.ns; ++i) {
-                const uint64_t o = h_off ? h_off[i] : (uint64_t)i * stride;
-                k.lo = std::min<uint64_t>(k.lo, o);
-                k.hi = std::max<uint64_t>(k.hi, o + (h_len ? h_len[i] : frame_len));
-            }
+            ether_span(h_off, h_len, stride, frame_len, k.s0, k.ns, &k.lo, &k.hi);
             maxb = std::max<uint64_t>(maxb, k.hi - k.lo);
         }
     }

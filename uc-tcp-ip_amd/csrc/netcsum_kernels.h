@@ -256,21 +256,30 @@ struct alignas(64) BurstPost {
     uint32_t n;            // frames (<= 4096)
     uint32_t pkt_len;      // strided forms: bytes present per slot
     uint32_t spw;          // frames per wave run
-    uint32_t form;         // bit 0 Tx; form >> 1: kBurstWhole / kBurstLive / kBurstOffLen
+    uint32_t form;         // bit 0 Tx; form >> 1: kBurstWhole / kBurstLive / kBurstOffLen, or kBurstEther
+                           // with kBurstEtherOff / kBurstEtherLen for the descriptors that are staged
     uint32_t udp_mode;     // Tx: PktBatchArgs::udp_tx_csum
     uint32_t rx_cfg;       // Rx: NETCSUM_RXCFG_* for the actions
-    uint32_t check;        // burst_post_check of the fields above: a read that tore the line fails it
-    uint32_t pad[4];
+    uint32_t check;        // burst_post_check of every other field: a read that tore the line fails it
+    uint32_t eth_cfg;      // kBurstEther: the demux's configuration, as EtherDemuxArgs names it (below);
+    uint32_t have_hw;      // 0 in every other post
+    uint32_t hw_lo;
+    uint32_t hw_hi;
 };
 static_assert(sizeof(BurstPost) == 64, "one line");
 constexpr uint64_t kBurstStop = ~0ull;
 constexpr uint32_t kBurstWhole = 0u, kBurstLive = 1u, kBurstOffLen = 2u;
+// Rx bursts of whole Ethernet frames (RxBurstEtherHost): the wave that owns a run classifies its frames
+// (netcsum_etherhead.h) and streams their datagrams from descriptors it keeps in registers. Frame starts
+// are off[i] with kBurstEtherOff, else i * stride; received lengths len[i] with kBurstEtherLen, else pkt_len.
+constexpr uint32_t kBurstEther = 3u, kBurstKindMask = 3u, kBurstEtherOff = 4u, kBurstEtherLen = 8u;
 constexpr int kBurstServerMaxBlocks = 16;
 __host__ __device__ __forceinline__ uint32_t burst_post_check(const BurstPost& p) {
-    const uint32_t d[11] = {(uint32_t)p.seq, (uint32_t)(p.seq >> 32), (uint32_t)p.ring, (uint32_t)(p.ring >> 32),
-                            p.stride, p.n, p.pkt_len, p.spw, p.form, p.udp_mode, p.rx_cfg};
+    const uint32_t d[15] = {(uint32_t)p.seq, (uint32_t)(p.seq >> 32), (uint32_t)p.ring, (uint32_t)(p.ring >> 32),
+                            p.stride, p.n, p.pkt_len, p.spw, p.form, p.udp_mode, p.rx_cfg,
+                            p.eth_cfg, p.have_hw, p.hw_lo, p.hw_hi};
     uint32_t h = 0x811C9DC5u;                               // FNV-1a over the dwords
-    for (int i = 0; i < 11; ++i) h = (h ^ d[i]) * 0x01000193u;
+    for (int i = 0; i < 15; ++i) h = (h ^ d[i]) * 0x01000193u;
     return h;
 }
 struct BurstServerArgs {
@@ -278,6 +287,7 @@ struct BurstServerArgs {
     unsigned long long* closed;    // [blocks]: set by a block that stops serving (device-written)
     uint8_t*            flags;     // Rx results (device aliases of coherent host memory)
     uint8_t*            act;
+    uint8_t*            l2;        // kBurstEther: the frames' NETCSUM_L2_* classes
     PktTxRecord*        rec;       // Tx records
     const uint64_t*     off;       // offset/length descriptors (staged in coherent host memory)
     const uint16_t*     len;

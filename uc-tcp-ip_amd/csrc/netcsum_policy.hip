@@ -418,6 +418,13 @@ void pkt_settle(const Tune& t, const PktJob& j, PktPlan& p) {
 // ----------------------------------------------------------- host bursts
 // The server's form for a burst (BurstPost::form >> 1 and its run length), or false when the burst is
 // outside the run-stream kernel's domain (the launch path takes it).
+// The server's run length: one run per wave of the grid until the runs reach 16 frames (Ether bursts,
+// whose datagrams the server's waves find themselves, take it as it is: their tail is the offset/length
+// form's, which fits any layout).
+uint32_t server_run(uint32_t n_pkt) {
+    return std::max<uint32_t>(1u, std::min<uint32_t>(16u, (n_pkt + 4u * kServerBlocks - 1u) / (4u * kServerBlocks)));
+}
+
 bool server_form(const uint64_t* h_off, uint64_t stride, CPU_INT16U pkt_len, uint32_t n_pkt, uint32_t* form, uint32_t* spw) {
     netcsum::PktBatchArgs a{};
     a.off = h_off;
@@ -425,7 +432,7 @@ bool server_form(const uint64_t* h_off, uint64_t stride, CPU_INT16U pkt_len, uin
     a.stride = stride;
     a.len_u = pkt_len;
     a.n = n_pkt;
-    uint32_t run = std::max<uint32_t>(1u, std::min<uint32_t>(16u, (n_pkt + 4u * kServerBlocks - 1u) / (4u * kServerBlocks)));
+    uint32_t run = server_run(n_pkt);
     if (h_off != nullptr) {
         *form = netcsum::kBurstOffLen;
         if (!netcsum::pkt_stream_supported(a, 0, 2)) return false;

@@ -87,18 +87,9 @@ __device__ __forceinline__ uint32_t group_sum(const uint8_t* p, uint32_t lo, uin
 // A lane group finishes datagram i (all values below are uniform in the group; lane = its lane).
 // SUMS (Rx, RxBurstSums): the group also writes the datagram's NETCSUM_FRAG_SUM record (A.sums_out): a
 // fragment's payload [Fragment header end, tot) by the same group sum, 0 for anything else.
+// walk_at: the datagram's `avail` octets at p; walk_one: datagram i of the batch's descriptors.
 template <bool TX, bool SUMS = false>
-__device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint32_t lane) {
-    uint64_t off64;
-    uint32_t avail;
-    if (A.off) {
-        off64 = A.off[i];
-        avail = A.len[i];
-    } else {
-        off64 = (uint64_t)i * A.stride;
-        avail = A.len_u;
-    }
-    uint8_t* p = const_cast<uint8_t*>(A.base) + off64;
+__device__ __forceinline__ void walk_at(const PktBatchArgs& A, uint32_t i, uint8_t* p, uint32_t avail, uint32_t lane) {
     if (avail < 40u || (p[0] >> 4) != 6u) {
         return;                                     // not IPv6: the batch kernel's flag stands
     }
@@ -177,6 +168,19 @@ __device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint
     }
 }
 
+template <bool TX, bool SUMS = false>
+__device__ __forceinline__ void walk_one(const PktBatchArgs& A, uint32_t i, uint32_t lane) {
+    uint64_t off64;
+    uint32_t avail;
+    if (A.off) {
+        off64 = A.off[i];
+        avail = A.len[i];
+    } else {
+        off64 = (uint64_t)i * A.stride;
+        avail = A.len_u;
+    }
+    walk_at<TX, SUMS>(A, i, const_cast<uint8_t*>(A.base) + off64, avail, lane);
+}
 
 // The calling wave's datagrams s0 + k whose lane k has `need` set, four at a time by its 16-lane
 // groups (every lane of the wave must be active).
@@ -195,6 +199,34 @@ __device__ __forceinline__ void walk_wave(const PktBatchArgs& A, uint32_t s0, bo
         }
         if (j != ~0u) {
             walk_one<TX, SUMS>(A, s0 + j, lane % kLanes);
+        }
+    }
+}
+
+// The same for a wave that keeps its datagrams' descriptors in registers and has none in memory (the
+// burst server's Ether form): lane k holds datagram s0 + k's address `at` and octets present `avail`,
+// and a group fetches its datagram's from lane j (ds_bpermute, by all 64 lanes: a group without a
+// datagram this round reads its own lane's).
+template <bool TX>
+__device__ __forceinline__ void walk_wave_regs(const PktBatchArgs& A, uint32_t s0, bool need, uint32_t lane, uintptr_t at,
+                                               uint32_t avail) {
+    const uint32_t grp = lane / kLanes;
+    uint64_t m = __ballot(need);
+    while (m != 0u) {
+        uint32_t j = ~0u;
+#pragma unroll
+        for (uint32_t g = 0; g < 64u / kLanes; ++g) {
+            if (m != 0u) {
+                j = (g == grp) ? (uint32_t)__builtin_ctzll(m) : j;
+                m &= m - 1u;
+            }
+        }
+        const int src = (int)(j != ~0u ? j : lane);
+        const uint64_t pj = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)((uint64_t)at >> 32), src, 64) << 32) |
+                            (uint32_t)__shfl((int)(uint32_t)at, src, 64);
+        const uint32_t aj = (uint32_t)__shfl((int)avail, src, 64);
+        if (j != ~0u) {
+            walk_at<TX>(A, s0 + j, reinterpret_cast<uint8_t*>((uintptr_t)pj), aj, lane % kLanes);
         }
     }
 }
