@@ -1,7 +1,8 @@
 /*
  * netcsum_ether.h — the layer-2 classification rules of NetUtil_MI355X_RxBurstEther
- * (netcsum_mi355x.h (2b'''')), stated once: the demux kernel (csrc/netcsum_ether.hip) and the host
- * logic (host/netcsum_ether.c) both include this file. Plain C99; under hipcc NETCSUM_L2_FN adds
+ * (netcsum_mi355x.h (2b'''')) and the Tx frame rule of NetUtil_MI355X_TxBurstEther ((2b'''''),
+ * NetCsum_L2TxClass below), each stated once: the demux kernels (csrc/netcsum_ether.hip), the burst
+ * server's Ether forms and the host logic (host/netcsum_ether.c) all include this file. Plain C99; under hipcc NETCSUM_L2_FN adds
  * __host__ __device__.
  *
  * The rules are those of the reference's 802.x receive path, in its order of checks (the first check
@@ -93,6 +94,21 @@ NETCSUM_L2_FN uint32_t NetCsum_L2Class(uint32_t len, const uint32_t w[6], uint32
     if (NetCsum_L2Octet(w, 16u) != 0x03u) return NETCSUM_L2_INV_LLC_CTRL;
     if ((w[4] >> 8) != 0u) return NETCSUM_L2_INV_SNAP_CODE;       /* octets 17-19                        */
     return NetCsum_L2TypeClass(NetCsum_L2Net16(w, 20u), 0);
+}
+
+/*
+ * The class of a frame of `len` octets about to be transmitted (NetUtil_MI355X_TxBurstEther,
+ * netcsum_mi355x.h (2b''''')), from the same six words: what NetIF_802x_Tx built (IF/net_if_802x.c:2643-2778).
+ * A frame shorter than NETCSUM_L2_FRAME_MIN did not come from the 802.x layer, which pads every frame to
+ * it (NetIF_802x_TxPktPrepareFrame, :2764-2778): INV_FRAME_SIZE from `len` alone. No address checks: the
+ * destination is what ARP / NDP resolved, broadcast or a group, the source the interface's own address
+ * written by the stack, so the INV_ADDR_* classes are never produced. The reference transmits Ethernet II
+ * only (:2691-2761): the type at +12 names the class, and every other value — the 802.3 length form
+ * (<= 1500) included, whose Rx length check assumes an FCS a Tx frame does not carry — is INV_ETHER_TYPE.
+ */
+NETCSUM_L2_FN uint32_t NetCsum_L2TxClass(uint32_t len, const uint32_t w[6]) {
+    if (len < NETCSUM_L2_FRAME_MIN) return NETCSUM_L2_INV_FRAME_SIZE;
+    return NetCsum_L2TypeClass(NetCsum_L2Net16(w, 12u), 1);
 }
 
 /* Octets of layer-2 header in front of a class's payload: 14 / 22, 0 for the INV_* classes. */

@@ -586,6 +586,60 @@ NET_ERR  NetUtil_MI355X_RxBurstEtherTally  (const uint8_t   *h_l2,
                                             uint32_t        *ctr);
 
 /* ============================================================================================
+ * (2b''''') Tx bursts of Ethernet frames: checksum fields filled in place, from the frame.
+ *
+ * TxBurst takes datagrams that start at the IP header. A driver's Tx queue holds what NetIF_802x_Tx
+ * built: an Ethernet II header of 14 octets in front of the datagram (IF/net_if_802x.c:2691-2761; the
+ * reference never transmits 802.3 / SNAP), zero padding up to 60 octets (NetIF_802x_TxPktPrepareFrame,
+ * :2764-2778), and ARP frames among the IP ones. TxBurstEther takes those frames as they are.
+ *
+ * Frames are addressed as RxBurstEther's, d_off == NULL with d_len != NULL included (slots at a pitch
+ * with per-frame lengths). The Tx rule (NetCsum_L2TxClass, netcsum_ether.h), in order:
+ *   1. len < 60: INV_FRAME_SIZE, from len alone — no octet of the frame is read or written (the 802.x
+ *      layer pads every frame to NET_IF_802x_FRAME_MIN_SIZE, so a shorter one is not its work).
+ *   2. No address checks: the destination is what ARP / NDP resolved, broadcast or a group, the source
+ *      the interface's own address. The INV_ADDR_* classes are never produced.
+ *   3. the big-endian word at +12: 0x0800 ETHER_IPV4, 0x86DD ETHER_IPV6, 0x0806 ETHER_ARP, any other
+ *      value INV_ETHER_TYPE — values <= 1500, the 802.3 length form, included: the Tx path has no such
+ *      frames and the Rx length check (len - 18) assumes an FCS a Tx frame does not carry. The header
+ *      is 14 octets.
+ *
+ * d_l2[i] (required) receives the class. d_flags[i] (optional) is byte for byte what TxBurst writes for
+ * the datagram at frame + 14 with len - 14 octets present; for a frame that carries no datagram to
+ * finalize (ARP, INV_*, an IP type whose datagram's version nibble is another's) it is what TxBurst
+ * writes for a datagram of no octets. The only octets that ever change are the checksum fields TxBurst
+ * would write in those datagrams, under (2b'')'s UDP 0 / 0xFFFF policy: padding, the Ethernet header,
+ * ARP and INV_* frames and the gaps between slots keep every byte. Frames must not overlap one another.
+ *
+ * Two launches on the caller's stream: ether_tx_demux_kernel (one lane per frame, RxBurstEther's head
+ * load with the Tx rule: the class, and the datagram's offset/length descriptor in this thread's scratch
+ * for the stream, past everything the Tx batch itself leases there; the capture rule is the Tx
+ * records'), then the offset/length TxBurst over the descriptors, unchanged.
+ * NetUtil_MI355X_LastLaunch() reads "ether_tx_demux b=<blocks> | " followed by TxBurst's string.
+ *
+ * Checks before any device work: NULL d_l2 or d_base with n_frame != 0 NET_ERR_FAULT_NULL_PTR;
+ * n_frame > 0x7FFFFFFF NET_UTIL_ERR_MI355X_INVALID_ARG; n_frame == 0 succeeds without a launch.
+ *
+ * TxBurstEtherHost ((2e) below): the same over a ring in host memory, in place through the resident
+ * burst server from a pinned ring, else by the copy pipeline.
+ * EtherTxClass: the rule on one frame in host memory, host logic (*p_hdr_len, optional: 14, or 0 for
+ * the INV_* classes). RxBurstEtherTally tallies any class array, a Tx burst's too.
+ * ============================================================================================ */
+NET_ERR  NetUtil_MI355X_TxBurstEther       (void            *d_base,
+                                            const uint64_t  *d_off,
+                                            const uint16_t  *d_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
+                                            uint8_t         *d_flags,
+                                            uint8_t         *d_l2,
+                                            void            *hip_stream);
+
+uint8_t  NetUtil_MI355X_EtherTxClass       (const void      *frame,
+                                            uint16_t         len,
+                                            uint16_t        *p_hdr_len);
+
+/* ============================================================================================
  * (2e) Host-memory forms (the path starts in NIC Rx buffers, IF/net_if.c:6593,
  * and socket Tx buffers, Source/net_sock.c:5531). Same arguments and results as the device forms
  * above with every pointer in HOST memory. The call splits the batch into n_chunks chunks and
@@ -685,6 +739,32 @@ NET_ERR  NetUtil_MI355X_RxBurstEtherHost   (const void      *h_base,
                                             uint32_t         eth_cfg,
                                             const uint8_t   *hw_addr,
                                             uint8_t         *h_action,
+                                            uint8_t         *h_flags,
+                                            uint8_t         *h_l2,
+                                            uint32_t         n_chunks);
+
+/* TxBurstEther ((2b''''') above) over frames in host memory — the driver's Tx ring itself; h_off == NULL
+ * with h_len != NULL is allowed as there.
+ * Copy pipeline: per chunk the frames' span and descriptors go H2D, the device form runs on the chunk's
+ * copy, one 8-B record of the fields written per frame, l2 and flags (optional) come back D2H, and the
+ * call writes the recorded fields into the ring at frame + 14 + position — nothing else of the ring is
+ * written. n_chunks 0: TxBurstHost's choice.
+ * In place: with n_chunks 0, n_frame <= 4096, the frames' span inside ONE pinned allocation of <= 64 MiB,
+ * NETCSUM_TUNE_BURST_ZERO_COPY 3 (the default) and a burst TxBurstHost's zero-copy path would accept, the
+ * burst is posted to the resident burst server as a Tx Ether form: the wave that owns a run of frames
+ * classifies them by the Tx rule, stores the classes and streams their datagrams into 8-B records in
+ * coherent pinned memory the call polls; the host applies each record at the frame's start + 14 (the
+ * device never writes the ring), and datagrams flagged NETCSUM_PKT_EXT_HDR (IPv6 chains past the kernel's
+ * window) are finished by the copy path as an offset/length batch of those datagrams.
+ * NetUtil_MI355X_LastLaunch() then reads "ether_tx_demux b=<server blocks> | burst_server_kernel tx
+ * form=ether pkts_per_wave=<K> zero-copy", plus " +copy path for <m> EXT_HDR datagrams" when some went
+ * there. Checks, their order, error codes and the resulting bytes do not depend on the path. */
+NET_ERR  NetUtil_MI355X_TxBurstEtherHost   (void            *h_base,
+                                            const uint64_t  *h_off,
+                                            const uint16_t  *h_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
                                             uint8_t         *h_flags,
                                             uint8_t         *h_l2,
                                             uint32_t         n_chunks);

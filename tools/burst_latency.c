@@ -20,7 +20,8 @@
  *                      place (_auto_copy: the same call under NETCSUM_TUNE_BURST_ZERO_COPY 0, the copy
  *                      pipeline)
  * and a check that every Rx action is DELIVER and every frame's class ETHER_IPV4. One JSON line per n on
- * stdout.
+ * stdout. With the argument "txether": the Tx Ether mode (tx_ether_only below), TxBurstEtherHost on the
+ * same slots against TxBurstHost at +14.
  *
  * Built here (the binary travels with the tree; tools/build/ is git-ignored), run on the GPU box:
  *   gcc -O2 -std=c11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tools/burst_latency.c \
@@ -115,7 +116,7 @@ static void build(uint8_t *slot)
     tcp[16] = tcp[17] = 0;
 }
 
-typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST, RX_ETHER_HOST } kind_t;
+typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST, RX_ETHER_HOST, TX_ETHER_HOST } kind_t;
 
 static uint8_t *g_dring, *g_hring, *g_dact, *g_hact, *g_hl2;
 static uint16_t *g_hlen;                                        /* received lengths: FRAME each */
@@ -143,6 +144,9 @@ static void call(kind_t k, uint32_t n)
         break;
     case RX_ETHER_HOST:
         NET_OK(NetUtil_MI355X_RxBurstEtherHost(g_hring, NULL, g_hlen, SLOT, 0, n, 0u, 0u, NULL, g_hact, NULL, g_hl2, chunks));
+        break;
+    case TX_ETHER_HOST:
+        NET_OK(NetUtil_MI355X_TxBurstEtherHost(g_hring, NULL, g_hlen, SLOT, 0, n, NULL, g_hl2, chunks));
         break;
     }
 }
@@ -217,6 +221,39 @@ static int zc_only(void)
     return 0;
 }
 
+/* "txether": the Tx Ether mode beside the Rx Ether one. Bursts of 1 / 64 / 1024 frames of 1514 octets from +0
+ * of the same pinned slots through TxBurstEtherHost with n_chunks 0 — in place by the resident server
+ * (tx_ether_host_auto) and under NETCSUM_TUNE_BURST_ZERO_COPY 0, the copy pipeline (_auto_copy) — against
+ * what a driver could do before: TxBurstHost at ring + 14 with a fixed pkt_len (tx_host_auto), on the same
+ * ring in the same run. Five interleaved repetitions, one JSON line each (medians of REPS calls), and a
+ * check that every class is ETHER_IPV4. */
+static int tx_ether_only(void)
+{
+    static const uint32_t sizes[] = {1u, 64u, 1024u};
+    int rep, ok = 1;
+    uint32_t s, i;
+    g_chunks = 0u;
+    for (rep = 0; rep < 5; ++rep) {
+        printf("{\"rep\": %d", rep);
+        for (s = 0; s < 3; ++s) {
+            const uint32_t n = sizes[s];
+            memset(g_hl2, 0xEE, n);
+            printf(", \"tx_host_auto_%u_us\": %.2f", n, time_us(TX_HOST, n));
+            printf(", \"tx_ether_host_auto_%u_us\": %.2f", n, time_us(TX_ETHER_HOST, n));
+            for (i = 0; i < n; ++i) ok &= g_hl2[i] == NETCSUM_L2_ETHER_IPV4;
+            NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, 0));
+            memset(g_hl2, 0xEE, n);
+            printf(", \"tx_ether_host_auto_copy_%u_us\": %.2f", n, time_us(TX_ETHER_HOST, n));
+            NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, 3));
+            for (i = 0; i < n; ++i) ok &= g_hl2[i] == NETCSUM_L2_ETHER_IPV4;
+        }
+        printf(", \"all_ether_ipv4\": %s}\n", ok ? "true" : "false");
+        fflush(stdout);
+    }
+    NetUtil_MI355X_ThreadRelease();
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     static const uint32_t sizes[] = {1u, 10u, 16u, 32u, 64u, 128u, 256u, 1024u, 4096u, 16384u, 65536u, 262144u};
@@ -236,6 +273,7 @@ int main(int argc, char **argv)
     NET_OK(NetUtil_MI355X_TxBurstHost(g_hring + IP_AT, NULL, NULL, SLOT, DGRAM, NMAX, NULL, 8u));   /* valid sums */
     HIP_OK(hipMemcpy(g_dring, g_hring, bytes, hipMemcpyHostToDevice));
     if (argc > 1 && strcmp(argv[1], "zc") == 0) return zc_only();
+    if (argc > 1 && strcmp(argv[1], "txether") == 0) return tx_ether_only();
     for (s = 0; s < sizeof sizes / sizeof sizes[0]; ++s) {
         const uint32_t n = sizes[s];
         double rx_dev, tx_dev, rx_host, tx_host;

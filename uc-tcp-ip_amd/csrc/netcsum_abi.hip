@@ -882,6 +882,67 @@ NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, c
     return NET_UTIL_ERR_NONE;
 }
 
+// Tx burst of Ethernet frames: the Tx demux pass (netcsum_ether.hip ether_tx_demux_kernel) writes each
+// frame's class and the offset/length descriptor of the datagram behind its Ethernet II header into this
+// thread's scratch for the stream, then TxBurst's offset/length batch runs over the descriptors,
+// unchanged. One lease for both steps, as RxBurstEther's, but the descriptors sit past everything
+// pkt_batch leases in the same slot for a Tx batch: the 256-B header, the two-pass form's 8-B record per
+// frame and the deferred-run list (at most 4 B per frame + 16). The capture rule is the Tx records'.
+// d_fieldpos / d_rec (the host-memory form's chunks; both or neither, d_fieldpos zeroed by the caller):
+// the fields each datagram had written, gathered into 8-B records while the descriptors are leased.
+extern "C++" NET_ERR nchost::tx_burst_ether(const Tune& t, void* d_base, const uint64_t* d_off, const uint16_t* d_len,
+                                            uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* d_flags,
+                                            uint8_t* d_l2, hipStream_t hs, uint32_t* d_fieldpos, uint64_t* d_rec) {
+    if (n_frame != 0 && (d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    int dev = 0;
+    NC_HIP(hipGetDevice(&dev));
+    const size_t n = n_frame;
+    const size_t o_off = (256u + 8u * n + 4u * n + 16u + 255u) & ~(size_t)255u;   // past pkt_batch's own Tx scratch
+    const size_t o_len = (o_off + 8u * n + 255u) & ~(size_t)255u;
+    ScratchLease scratch;
+    NC_HIP(scratch.acquire(dev, hs, o_len + 2u * n));
+    uint8_t* sp = static_cast<uint8_t*>(scratch.ptr());
+    netcsum::EtherDemuxArgs a{};
+    a.base = static_cast<const uint8_t*>(d_base);
+    a.off = d_off;
+    a.len = d_len;
+    a.stride = stride;
+    a.len_u = frame_len;
+    a.n = n_frame;
+    a.l2_out = d_l2;
+    a.off_out = reinterpret_cast<uint64_t*>(sp + o_off);
+    a.len_out = reinterpret_cast<uint16_t*>(sp + o_len);
+    NC_HIP(netcsum::launch_ether_tx_demux(a, hs));
+    PktJob j = pkt_job(d_base, a.off_out, a.len_out, 0, 0, n_frame, d_flags, hs);
+    j.tx = true;
+    j.udp_mode = 2u;
+    j.fieldpos = d_fieldpos;
+    const NET_ERR e = pkt_batch(t, j);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    if (d_rec != nullptr) {
+        netcsum::PktBatchArgs g{};
+        g.base = static_cast<const uint8_t*>(d_base);
+        g.off = a.off_out;
+        g.n = n_frame;
+        g.fieldpos_out = d_fieldpos;
+        NC_HIP(netcsum::launch_pkt_field_gather(g, d_rec, hs));
+    }
+    NC_HIP(scratch.end());
+    char desc[256];
+    snprintf(desc, sizeof desc, "ether_tx_demux b=%u | %.220s", netcsum::ether_demux_blocks(n_frame), netcsum::last_launch());
+    netcsum::set_last_launch(desc);
+    return NET_UTIL_ERR_NONE;
+}
+
+NET_ERR NetUtil_MI355X_TxBurstEther(void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                                    CPU_INT16U frame_len, uint32_t n_frame, uint8_t* d_flags, uint8_t* d_l2,
+                                    void* hip_stream) {
+    return tx_burst_ether(tls_tune, d_base, d_off, d_len, stride, frame_len, n_frame, d_flags, d_l2,
+                          static_cast<hipStream_t>(hip_stream), nullptr, nullptr);
+}
+
 uint8_t NetUtil_MI355X_RxAction(uint8_t flags, uint8_t proto, int ipv6, uint32_t rx_cfg) {
     return (uint8_t)netcsum::rx_action(flags, proto, ipv6 != 0, rx_cfg);
 }

@@ -37,7 +37,29 @@ __global__ __launch_bounds__(kEtherDemuxBlock) void ether_demux_kernel(const Eth
     A.len_out[i] = (uint16_t)h.ip;
 }
 
+// The Tx demux of NetUtil_MI355X_TxBurstEther ((2b''''')): the same lane per frame and head load with the
+// Tx rule (NetCsum_L2TxClass: the frame's length, then the Ethernet II type; octets 12 - 14 decide
+// everything, the same one or two sectors per frame), and the descriptor of the datagram TxBurst is to
+// finalize: {start + 14, len - 14}, or {start, 0} for a frame that carries none. It writes nothing to
+// the ring.
+__global__ __launch_bounds__(kEtherDemuxBlock) void ether_tx_demux_kernel(const EtherDemuxArgs A) {
+    const uint32_t i = blockIdx.x * kEtherDemuxBlock + threadIdx.x;
+    if (i >= A.n) return;
+    const uint64_t o = A.off ? A.off[i] : (uint64_t)i * A.stride;
+    const uint32_t len = A.len ? A.len[i] : A.len_u;
+    const EtherHead h = ether_head_tx(reinterpret_cast<uintptr_t>(A.base) + o, len);
+    A.l2_out[i] = (uint8_t)h.cls;
+    A.off_out[i] = h.ip ? o + NETCSUM_L2_HDR_ETHER : o;
+    A.len_out[i] = (uint16_t)h.ip;
+}
+
 }  // namespace
+
+hipError_t launch_ether_tx_demux(const EtherDemuxArgs& a, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(ether_tx_demux_kernel, dim3(ether_demux_blocks(a.n)), dim3(kEtherDemuxBlock), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_ether_demux(const EtherDemuxArgs& a, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;

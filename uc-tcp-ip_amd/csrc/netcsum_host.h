@@ -124,6 +124,14 @@ PktJob pkt_job(const void* base, const uint64_t* off, const uint16_t* len, uint6
                uint8_t* flags, void* hip_stream);
 NET_ERR pkt_batch(const Tune& t, const PktJob& j);
 
+// TxBurstEther on device-visible memory (netcsum_abi.hip): the public entry point, and — with d_fieldpos
+// (zeroed by the caller) and d_rec — a chunk of the host-memory form, whose written fields come back as
+// one 8-B record per frame (launch_pkt_field_gather over the datagrams' descriptors: positions count
+// from frame + 14).
+NET_ERR tx_burst_ether(const Tune& t, void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                       CPU_INT16U frame_len, uint32_t n_frame, uint8_t* d_flags, uint8_t* d_l2, hipStream_t hs,
+                       uint32_t* d_fieldpos, uint64_t* d_rec);
+
 // 16 blocks x 4 waves: a block's leader polls the post line (16 64-B reads per poll round); 4 blocks
 // of 16 waves were slower from 10 frames up (tools/burst_latency.c, 64 frames 14.8 us against 13.1 us
 // for a launch per burst: 16 waves on one CU queue their PCIe reads)

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/netcsum_ether.h"
 #include "netcsum_device.h"
 #include "netcsum_host.h"
 
@@ -626,12 +627,12 @@ static NET_ERR burst_server_run(const Tune& t, HostCtx& c, netcsum::BurstPost p,
 
 // NetUtil_MI355X_LastLaunch after a zero-copy burst: which path served it (the tests check that the
 // zero-copy path, not the copy pipeline, was taken)
-// (an Ether burst: "ether_demux b=<blocks> | " in front, RxBurstEther's shape, with the server's blocks,
-// whose waves did the demux)
+// (an Ether burst: "ether_demux b=<blocks> | " — Tx: "ether_tx_demux b=<blocks> | " — in front, the
+// device forms' shape, with the server's blocks, whose waves did the demux)
 static void server_launch_name(uint32_t form, uint32_t spw, bool tx) {
     char d[128];
     const bool ether = (form & netcsum::kBurstKindMask) == netcsum::kBurstEther;
-    int k = ether ? snprintf(d, sizeof d, "ether_demux b=%d | ", kServerBlocks) : 0;
+    int k = ether ? snprintf(d, sizeof d, "%s b=%d | ", tx ? "ether_tx_demux" : "ether_demux", kServerBlocks) : 0;
     snprintf(d + k, sizeof d - (size_t)k, "burst_server_kernel %s form=%s pkts_per_wave=%u zero-copy", tx ? "tx" : "rx",
              ether ? "ether" : form == netcsum::kBurstWhole ? "whole" : form == netcsum::kBurstLive ? "live" : "offlen", spw);
     netcsum::set_last_launch(d);
@@ -1168,6 +1169,205 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
         NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
     }
     for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
+    guard.done = true;
+    return NET_UTIL_ERR_NONE;
+}
+
+static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
+                                   uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
+                                   uint32_t n_chunks);
+
+// A Tx Ether burst over a pinned ring in place, by the resident server's Tx Ether form
+// (netcsum_pktstream.hip pkt_ether_run<TX, REC>): the wave that owns a run classifies its frames by the Tx
+// rule, stores the classes and streams the datagrams in the record-producing Tx instantiation; classes
+// and records arrive in coherent memory behind 0xFF sentinels (no class is >= 16, a record's store byte is
+// 0..3), the host polls both and applies each record at the frame's start + 14, exactly as
+// tx_burst_zero_copy does for datagrams. Nothing on the device writes the ring. Datagrams flagged EXT_HDR
+// (IPv6 chains past the kernel's window) are finished by the copy path as an offset/length batch of those
+// datagrams. Taken under rx_burst_ether_zero_copy's conditions, for a burst tx_burst_zero_copy would accept
+// as an offset/length one (the records come from the run-stream kernel only). *taken = false: the caller
+// takes the copy pipeline.
+static NET_ERR tx_burst_ether_zero_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
+                                        uint64_t stride, CPU_INT16U frame_len, uint32_t n, uint8_t* h_flags, uint8_t* h_l2,
+                                        bool* taken) {
+    *taken = false;
+    if (n > kBurstZC || t.kernel == 2) return NET_UTIL_ERR_NONE;
+    const int tb = t.pkt_bound;
+    if (tb == 0 || tb == 3) return NET_UTIL_ERR_NONE;        // (offset/length runs: the live-piece forms only)
+    uint64_t lo = 0, hi = 0;
+    ether_span(h_off, h_len, stride, frame_len, 0u, n, &lo, &hi);
+    if (hi <= lo || hi - lo > kBurstZCSpan) return NET_UTIL_ERR_NONE;
+    const uint8_t* d_lo = pinned_alias(static_cast<const uint8_t*>(h_base) + lo, hi - lo);
+    if (d_lo == nullptr) return NET_UTIL_ERR_NONE;
+    *taken = true;
+    NET_ERR e = ensure_burst(c);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    uint32_t form = netcsum::kBurstEther;
+    const uint32_t spw = server_run(n);                     // (as the offset/length form)
+    if (h_off) {
+        std::memcpy(c.h_burst + kBurstOff, h_off, (size_t)n * 8u);
+        form |= netcsum::kBurstEtherOff;
+    }
+    if (h_len) {
+        std::memcpy(c.h_burst + kBurstLen, h_len, (size_t)n * 2u);
+        form |= netcsum::kBurstEtherLen;
+    }
+    uint8_t* hr = c.h_burst + kBurstRec;
+    uint8_t* hl = c.h_burst + kBurstL2;
+    std::memset(hr, 0xFF, (size_t)n * 8u);
+    std::memset(hl, 0xFF, n);
+    netcsum::BurstPost post{};                              // (every field this form does not use: 0)
+    post.ring = reinterpret_cast<uint64_t>(d_lo - lo);      // the base's alias: offsets count from it
+    post.stride = (uint32_t)stride;
+    post.n = n;
+    post.pkt_len = frame_len;
+    post.spw = spw;
+    post.form = (form << 1) | 1u;
+    post.udp_mode = 2u;
+    server_launch_name(form, spw, true);
+    e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hr + 8u * i + 7u) != 0xFFu &&
+                                                              *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    std::memcpy(h_l2, hl, n);
+    uint8_t* hb = static_cast<uint8_t*>(h_base);
+    const uint64_t* rec = reinterpret_cast<const uint64_t*>(hr);
+    std::vector<uint64_t> walk_off;
+    std::vector<uint16_t> walk_len;
+    std::vector<uint32_t> walk_idx;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t r = rec[i];                          // PktTxRecord: vals | l4_off << 32 | flags << 48 | store << 56
+        const uint32_t flags = (uint32_t)(r >> 48) & 0xFFu, store = (uint32_t)(r >> 56);
+        const uint64_t o = (h_off ? h_off[i] : (uint64_t)i * stride) + NETCSUM_L2_HDR_ETHER;
+        if (flags & NETCSUM_PKT_EXT_HDR) {                  // (only an IP frame's datagram gets this flag)
+            walk_off.push_back(o);
+            walk_len.push_back((uint16_t)((h_len ? h_len[i] : frame_len) - NETCSUM_L2_HDR_ETHER));
+            walk_idx.push_back(i);
+            continue;
+        }
+        uint8_t* p = hb + o;
+        const uint16_t ip = (uint16_t)r, l4 = (uint16_t)(r >> 16);
+        if (store & 1u) std::memcpy(p + 10, &ip, 2);
+        if (store & 2u) std::memcpy(p + ((r >> 32) & 0xFFFFu), &l4, 2);
+        if (h_flags) h_flags[i] = (uint8_t)flags;
+    }
+    if (!walk_off.empty()) {                                // the rare long IPv6 chains: the copy path
+        const uint32_t m = (uint32_t)walk_off.size();
+        std::vector<uint8_t> fl(m);
+        char zc_name[256];
+        snprintf(zc_name, sizeof zc_name, "%s", NetUtil_MI355X_LastLaunch());
+        PktJob rest = pkt_job(h_base, walk_off.data(), walk_len.data(), 0, 0, m, h_flags ? fl.data() : nullptr, nullptr);
+        rest.tx = true;
+        rest.udp_mode = 2u;
+        e = pkt_host_copy(t, rest, 1u);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        char d[256];
+        snprintf(d, sizeof d, "%.180s +copy path for %u EXT_HDR datagrams", zc_name, m);
+        netcsum::set_last_launch(d);
+        if (h_flags) {
+            for (uint32_t k = 0; k < m; ++k) h_flags[walk_idx[k]] = fl[k];
+        }
+    }
+    return NET_UTIL_ERR_NONE;
+}
+
+// TxBurstEther over frames in host memory: RxBurstEtherHost's chunk loop (ether_span per chunk) with the Tx
+// return path of pkt_host_copy. Per chunk: H2D of the frames' span and descriptors, the device form on the
+// chunk's copy (Tx demux, the offset/length Tx batch, the field gather over the datagrams' descriptors),
+// D2H of one 8-B record per frame, the classes and the flags; once the chunk's stream has drained the
+// host writes the recorded fields into its own ring at frame + 14 + position. Nothing else of the ring
+// is written. A burst from a pinned ring (n_chunks 0, at most 4096 frames in one pinned allocation,
+// TUNE_BURST_ZERO_COPY 3) is served in place by the resident burst server instead
+// (tx_burst_ether_zero_copy). Checks, their order, error codes and the resulting bytes do not depend on
+// the path.
+NET_ERR NetUtil_MI355X_TxBurstEtherHost(void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                        CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
+                                        uint32_t n_chunks) {
+    if (n_frame != 0 && (h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    HostCtx* cp = nullptr;
+    NET_ERR e = host_ctx(&cp);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    const Tune& t = tune();
+    if (n_chunks == 0 && t.burst_zc == 3) {                  // a burst from a pinned ring: in place
+        bool taken = false;
+        e = tx_burst_ether_zero_copy(t, *cp, h_base, h_off, h_len, stride, frame_len, n_frame, h_flags, h_l2, &taken);
+        if (taken) return e;
+    }
+    return tx_burst_ether_copy(t, *cp, h_base, h_off, h_len, stride, frame_len, n_frame, h_flags, h_l2, n_chunks);
+}
+
+// The copy pipeline of TxBurstEtherHost (above).
+static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
+                                   uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
+                                   uint32_t n_chunks) {
+    NET_ERR e = NET_UTIL_ERR_NONE;
+    // chunks: TxBurstHost's choice (the host's field write-back overlaps the later chunks' copies)
+    if (n_chunks == 0) n_chunks = std::min(16u, std::max(1u, n_frame / 16384u));
+    if (n_frame / n_chunks > (1u << 28)) n_chunks = (n_frame >> 28) + 1u;
+    std::vector<HostChunk> ch;
+    uint64_t maxb = plan_chunks(nullptr, nullptr, stride, frame_len, n_frame, n_chunks, ch);
+    if (h_off != nullptr || h_len != nullptr) {
+        maxb = 0;
+        for (HostChunk& k : ch) {
+            ether_span(h_off, h_len, stride, frame_len, k.s0, k.ns, &k.lo, &k.hi);
+            maxb = std::max<uint64_t>(maxb, k.hi > k.lo ? k.hi - k.lo : 0u);
+        }
+    }
+    const uint32_t per = ch[0].ns;
+    // device slot: [bytes | offsets | lengths | flags | classes | field positions | records];
+    // host slot: [offsets | lengths | records]
+    const size_t o_off = al256(maxb), o_len = o_off + al256(h_off ? (size_t)per * 8u : 0u);
+    const size_t o_fl = o_len + al256(h_len ? (size_t)per * 2u : 0u), o_l2 = o_fl + al256(per);
+    const size_t o_fp = o_l2 + al256(per), o_rec = o_fp + al256((size_t)per * 4u);
+    const size_t hs_len = al256(h_off ? (size_t)per * 8u : 0u);
+    const size_t hs_rec = hs_len + al256(h_len ? (size_t)per * 2u : 0u);
+    e = ensure_pipe(c, o_rec + al256((size_t)per * 8u), hs_rec + (size_t)per * 8u);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    PipeDrainOnExit guard{c};
+    uint8_t* hb = static_cast<uint8_t*>(h_base);
+    auto drain = [&](size_t k) -> NET_ERR {                  // chunk k's stream has finished: apply its records
+        NC_HIP(hipStreamSynchronize(c.pstream[k % 3u]));
+        apply_field_records(hb + NETCSUM_L2_HDR_ETHER, h_off, stride, ch[k].s0, ch[k].ns,
+                            reinterpret_cast<const uint64_t*>(c.h_pipe[k % 3u] + hs_rec));
+        return NET_UTIL_ERR_NONE;
+    };
+    for (size_t k = 0; k < ch.size(); ++k) {
+        const HostChunk& q = ch[k];
+        const int j = (int)(k % 3u);
+        hipStream_t st = c.pstream[j];
+        uint8_t* d = c.d_pipe[j];
+        if (k >= 3) {                                        // slot j's staging is free again
+            e = drain(k - 3u);
+            if (e != NET_UTIL_ERR_NONE) return e;
+        }
+        if (q.hi > q.lo) NC_HIP(hipMemcpyAsync(d, hb + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
+        if (h_off) {
+            uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
+            for (uint32_t i = 0; i < q.ns; ++i) h_o[i] = h_off[q.s0 + i] - q.lo;
+            NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
+        }
+        if (h_len) {
+            uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + hs_len);
+            std::memcpy(h_l, h_len + q.s0, (size_t)q.ns * 2u);
+            NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
+        }
+        uint32_t* d_fp = reinterpret_cast<uint32_t*>(d + o_fp);
+        uint64_t* d_rec = reinterpret_cast<uint64_t*>(d + o_rec);
+        NC_HIP(hipMemsetAsync(d_fp, 0, (size_t)q.ns * 4u, st));   // a frame no kernel wrote: no fields
+        // (a strided chunk's copy starts at its first slot: q.lo = s0 * stride, so slot i of the chunk is at i * stride)
+        e = tx_burst_ether(t, d, h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr,
+                           h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr, stride, frame_len, q.ns,
+                           h_flags ? d + o_fl : nullptr, d + o_l2, st, d_fp, d_rec);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
+        NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
+        NC_HIP(hipMemcpyAsync(c.h_pipe[j] + hs_rec, d_rec, (size_t)q.ns * 8u, hipMemcpyDeviceToHost, st));
+    }
+    for (size_t k = ch.size() > 3 ? ch.size() - 3 : 0; k < ch.size(); ++k) {
+        e = drain(k);
+        if (e != NET_UTIL_ERR_NONE) return e;
+    }
     guard.done = true;
     return NET_UTIL_ERR_NONE;
 }

@@ -269,7 +269,8 @@ struct alignas(64) BurstPost {
 static_assert(sizeof(BurstPost) == 64, "one line");
 constexpr uint64_t kBurstStop = ~0ull;
 constexpr uint32_t kBurstWhole = 0u, kBurstLive = 1u, kBurstOffLen = 2u;
-// Rx bursts of whole Ethernet frames (RxBurstEtherHost): the wave that owns a run classifies its frames
+// Bursts of whole Ethernet frames (RxBurstEtherHost; with bit 0 of the form, Tx: TxBurstEtherHost, the Tx
+// rule and one PktTxRecord per frame): the wave that owns a run classifies its frames
 // (netcsum_etherhead.h) and streams their datagrams from descriptors it keeps in registers. Frame starts
 // are off[i] with kBurstEtherOff, else i * stride; received lengths len[i] with kBurstEtherLen, else pkt_len.
 constexpr uint32_t kBurstEther = 3u, kBurstKindMask = 3u, kBurstEtherOff = 4u, kBurstEtherLen = 8u;
@@ -327,5 +328,8 @@ struct EtherDemuxArgs {
 constexpr uint32_t kEtherDemuxBlock = 256u;
 inline uint32_t ether_demux_blocks(uint32_t n) { return (n + kEtherDemuxBlock - 1u) / kEtherDemuxBlock; }
 hipError_t launch_ether_demux(const EtherDemuxArgs& a, hipStream_t s);
+// The demux ahead of a Tx burst of Ethernet frames (ether_tx_demux_kernel, NetCsum_L2TxClass): the same
+// arguments and outputs; eth_cfg and the interface's address are not looked at.
+hipError_t launch_ether_tx_demux(const EtherDemuxArgs& a, hipStream_t s);
 
 }  // namespace netcsum

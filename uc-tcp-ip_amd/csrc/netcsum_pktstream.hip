@@ -719,9 +719,13 @@ struct EtherRunArgs {
     uint8_t* l2;
 };
 
-template <int D, bool NT, int BND>
-__device__ __forceinline__ void pkt_ether_run(const PktBatchArgs& A, const EtherRunArgs& E, uint32_t spw, uint64_t run,
-                                              uint32_t w, uint32_t lane) {
+// TX / REC (the Tx Ether form, TxBurstEtherHost): the lane classifies by the Tx rule (ether_head_tx: the
+// length, then the Ethernet II type) and the datagram streams in the record-producing Tx instantiation,
+// one PktTxRecord per frame into rec — nothing is written to the ring, and a datagram flagged EXT_HDR is
+// left to the host (no walk here: REC), so the descriptors are needed in no register past the run.
+template <int D, bool NT, int BND, bool TX = false, bool REC = false>
+__device__ __forceinline__ void pkt_ether_run(const PktBatchArgs& A, const EtherRunArgs& E, uint32_t spw, PktTxRecord* rec,
+                                              uint64_t run, uint32_t w, uint32_t lane) {
     const uint64_t sb64 = run * spw;
     if (sb64 >= A.n) {
         return;
@@ -732,12 +736,17 @@ __device__ __forceinline__ void pkt_ether_run(const PktBatchArgs& A, const Ether
     const uint32_t i = mine ? s_begin + lane : s_begin;
     const uint64_t o = A.off ? A.off[i] : (uint64_t)i * A.stride;
     const uint32_t len = !mine ? 0u : A.len ? (uint32_t)A.len[i] : A.len_u;
-    const EtherHead h = ether_head((uintptr_t)A.base + o, len, E.eth_cfg, E.have_hw, E.hw_lo, E.hw_hi);
+    EtherHead h;
+    if constexpr (TX) {
+        h = ether_head_tx((uintptr_t)A.base + o, len);
+    } else {
+        h = ether_head((uintptr_t)A.base + o, len, E.eth_cfg, E.have_hw, E.hw_lo, E.hw_hi);
+    }
     if (mine) {
         E.l2[i] = (uint8_t)h.cls;
     }
-    pkt_vl_tail<D, NT, false, false, 0, BND, false, false, true>(A, spw, nullptr, run, w, lane, s_begin, nres,
-                                                                 h.ip ? o + NetCsum_L2HdrLen(h.cls) : o, h.ip);
+    pkt_vl_tail<D, NT, TX, REC, 0, BND, false, false, !REC>(A, spw, rec, run, w, lane, s_begin, nres,
+                                                            h.ip ? o + NetCsum_L2HdrLen(h.cls) : o, h.ip);
 }
 
 // The deferred pass of an offset/length batch: the runs its stream kernel listed (A.vl_list, count in
@@ -1052,7 +1061,8 @@ __global__ void __launch_bounds__(64) burst_done_kernel(const uint8_t* fl, const
 // blockIdx * 4 + w, + 4 * blocks, ... of the burst with the run-stream code above (mixed IPv4 / IPv6,
 // 4 pieces in flight), write the results into coherent host memory and release them. A burst of whole
 // Ethernet frames (kBurstEther) is demuxed by the same waves, each for its own runs, between the same
-// two barriers (pkt_ether_run: no pass, wait or hand-off of its own). A block stops
+// two barriers (pkt_ether_run: no pass, wait or hand-off of its own; a Tx burst of frames likewise, by the
+// Tx rule and into records). A block stops
 // when it has been idle for idle_ticks, when life_ticks have passed since it started (even while
 // bursts keep coming: the server's stream shares a hardware queue with other streams of the process,
 // GPU_MAX_HW_QUEUES, and their kernels wait behind it), or when it sees another block's closed mark
@@ -1174,7 +1184,13 @@ __global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
             }
             if (form & 1u) {
-                if ((form >> 1) == kBurstWhole) {
+                if (ether) {
+                    const EtherRunArgs E{0u, 0u, 0u, 0u, S.l2};
+                    const uint32_t runs = (A.n + spw - 1u) / spw;
+                    for (uint32_t r = blockIdx.x * 4u + w; r < runs; r += gridDim.x * 4u) {
+                        pkt_ether_run<4, true, 2, true, true>(A, E, spw, S.rec, r, w, lane);
+                    }
+                } else if ((form >> 1) == kBurstWhole) {
                     burst_serve<true, 0, false>(A, spw, S.rec, w, lane);
                 } else if ((form >> 1) == kBurstLive) {
                     burst_serve<true, 2, false>(A, spw, S.rec, w, lane);
@@ -1188,7 +1204,7 @@ __global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
                     const EtherRunArgs E{d[12], d[13], d[14], d[15], S.l2};
                     const uint32_t runs = (A.n + spw - 1u) / spw;
                     for (uint32_t r = blockIdx.x * 4u + w; r < runs; r += gridDim.x * 4u) {
-                        pkt_ether_run<4, true, 2>(A, E, spw, r, w, lane);
+                        pkt_ether_run<4, true, 2>(A, E, spw, nullptr, r, w, lane);
                     }
                 } else if ((form >> 1) == kBurstWhole) {
                     burst_serve<false, 0, false>(A, spw, nullptr, w, lane);

@@ -267,6 +267,12 @@ def lib() -> ctypes.CDLL:
     L.NetUtil_MI355X_EtherClass.restype = ctypes.c_uint8
     L.NetUtil_MI355X_RxBurstEtherTally.argtypes = [vp, u32, vp]
     L.NetUtil_MI355X_RxBurstEtherTally.restype = i32
+    L.NetUtil_MI355X_TxBurstEther.argtypes = [vp, vp, vp, u64, u16, u32, vp, vp, vp]
+    L.NetUtil_MI355X_TxBurstEther.restype = i32
+    L.NetUtil_MI355X_TxBurstEtherHost.argtypes = [vp, vp, vp, u64, u16, u32, vp, vp, u32]
+    L.NetUtil_MI355X_TxBurstEtherHost.restype = i32
+    L.NetUtil_MI355X_EtherTxClass.argtypes = [vp, u16, ctypes.POINTER(ctypes.c_uint16)]
+    L.NetUtil_MI355X_EtherTxClass.restype = ctypes.c_uint8
     L.NetUtil_MI355X_RxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, vp, vp, u32]
     L.NetUtil_MI355X_RxBurstHost.restype = i32
     L.NetUtil_MI355X_TxBurstHost.argtypes = [vp, vp, vp, u64, u16, u32, vp, u32]
@@ -715,6 +721,30 @@ def tx_burst(base, n, flags=None, off=None, lens=None, stride=0, pkt_len=0, stre
     return err
 
 
+def tx_burst_ether(base, n, l2, flags=None, off=None, lens=None, stride=0, frame_len=0, stream=None, check=True):
+    """NetUtil_MI355X_TxBurstEther: a Tx burst of whole Ethernet frames, finalized in place. `l2` receives
+    each frame's L2_* class by the Tx rule, `flags` what tx_burst gives for the datagram at frame + 14 (for
+    a frame that carries none, a datagram of no octets). `lens` may come without `off`: slots at `stride`."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(l2, n, "layer-2 classes")
+    err = lib().NetUtil_MI355X_TxBurstEther(_p(base), _p(off), _p(lens), stride, frame_len, n, _p(flags), _p(l2),
+                                            _stream(stream))
+    if check:
+        _check(err, "NetUtil_MI355X_TxBurstEther")
+    return err
+
+
+def ether_tx_class(frame, length=None):
+    """NetUtil_MI355X_EtherTxClass (host logic) of one frame (bytes) -> (L2_* class, header length 14 / 0).
+    length: the frame's octets, where they differ from len(frame)."""
+    frame = bytes(frame)
+    hb = HostBytes(frame)
+    hdr = ctypes.c_uint16(0xFFFF)
+    cls = lib().NetUtil_MI355X_EtherTxClass(hb.ptr, len(frame) if length is None else length, ctypes.byref(hdr))
+    return int(cls), int(hdr.value)
+
+
 def rx_action(flags, proto, ipv6, rx_cfg=0):
     """NetUtil_MI355X_RxAction (host logic): the burst action of one verdict."""
     return int(lib().NetUtil_MI355X_RxAction(flags, proto, int(bool(ipv6)), rx_cfg))
@@ -808,6 +838,18 @@ def rx_burst_ether_host(base, n, action, l2, flags=None, off=None, lens=None, st
                                                 _p(action), _p(flags), _p(l2), n_chunks)
     if check:
         _check(err, "NetUtil_MI355X_RxBurstEtherHost")
+    return err
+
+
+def tx_burst_ether_host(base, n, l2, flags=None, off=None, lens=None, stride=0, frame_len=0, n_chunks=0, check=True):
+    """NetUtil_MI355X_TxBurstEtherHost: tx_burst_ether over a ring and result arrays in host memory."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(l2, n, "layer-2 classes")
+    err = lib().NetUtil_MI355X_TxBurstEtherHost(_p(base), _p(off), _p(lens), stride, frame_len, n, _p(flags), _p(l2),
+                                                n_chunks)
+    if check:
+        _check(err, "NetUtil_MI355X_TxBurstEtherHost")
     return err
 
 
