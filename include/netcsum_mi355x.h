@@ -422,8 +422,14 @@ NET_ERR  NetUtil_MI355X_RxBurstTally       (const uint8_t   *h_action,
  * by the extension-header walk. d_sums must be 4-byte aligned (one record is one store), n_pkt at
  * most 2^30 - 1; the other arguments and their checks are RxBurst's.
  *
- * RxBurstSumsHost is RxBurstHost with h_sums; it always takes the copy pipeline (4 B more per frame
- * D2H): the resident burst server does not produce this output.
+ * RxBurstSumsHost is RxBurstHost with h_sums. A burst from a pinned ring is served in place by the
+ * resident burst server under RxBurstHost's conditions (n_chunks 0, at most 4096 frames in one pinned
+ * allocation of at most 64 MiB) with NETCSUM_TUNE_BURST_ZERO_COPY 3 (the default) and a layout the
+ * server streams; NetUtil_MI355X_LastLaunch() then reads "burst_server_kernel rx,sums form=<form>
+ * pkts_per_wave=<k> zero-copy". Every other call takes the copy pipeline (4 B more per frame D2H); the
+ * bytes are the same. The server that takes sums bursts is an instantiation of its own: a thread's
+ * server is relaunched as that one, once, by the thread's first sums burst, and from then on serves its
+ * bursts of every kind.
  *
  * FragSumCalc / FragSumVerify (host logic, no device work): frag[0 .. n_frag) are the records of one
  * datagram's fragments in reassembly order. The result equals DataCalc / DataVerify over a chain of
@@ -536,6 +542,28 @@ NET_ERR  NetUtil_MI355X_FragSumVerify      (const NETCSUM_FRAG_SUM *frag,
  * RxBurstEtherHost ((2e) below): the same from host memory. A burst of <= 4096 frames with n_chunks 0
  * from ONE pinned allocation is served in place by the resident burst server, whose waves do the demux
  * themselves; every other call takes the copy pipeline. The results are the same bytes either way.
+ *
+ * RxBurstEtherSums / RxBurstEtherSumsHost: RxBurstEther[Host] with the fragment payload sums of (2b''').
+ * The arguments are RxBurstEther[Host]'s in their order, with NETCSUM_FRAG_SUM *d_sums / *h_sums after
+ * d_l2 / h_l2. d_action, d_flags and d_l2 are byte for byte what RxBurstEther writes for the same call;
+ * d_sums[i] is what RxBurstSums writes for the datagram RxBurstEther hands to the checksum pass — frame
+ * + 14 or + 22 with len - 14 or - 22 octets present — and {0, 0} for every frame that hands it none: ARP,
+ * every INV_* class, and a frame whose type names one IP version and whose first nibble names the other
+ * (where RxBurstSums at frame + 14 would report a sum). A record's len comes from the IP header (total
+ * length / payload length), never from the octets received: padding to 60 octets and FCS octets are not
+ * summed. An IPv4 fragment whose header checksum fails gets its sum all the same. Checks: RxBurstEther's,
+ * then RxBurstSums' — NULL sums with n_frame != 0 NET_ERR_FAULT_NULL_PTR; sums not 4-byte aligned or
+ * n_frame > 2^30 - 1 NET_UTIL_ERR_MI355X_INVALID_ARG; n_frame == 0 succeeds without a launch. The device
+ * form is the demux launch, then RxBurstSums' offset/length launch over the descriptors (which lie above
+ * all that batch leases in the thread's scratch, as RxBurstEther's do; the lease and capture rules are
+ * RxBurstEther's); LastLaunch() reads "ether_demux b=<blocks> | " followed by RxBurstSums' string. The
+ * host form is served in place under RxBurstEtherHost's conditions, by the server instantiation that
+ * takes sums bursts ((2b''') above); LastLaunch() then reads "ether_demux b=16 | burst_server_kernel
+ * rx,sums form=ether pkts_per_wave=<k> zero-copy". Every other call takes the copy pipeline, which
+ * returns the records as a fourth region per chunk. This is the driver glue INTEGRATION §2 recommends:
+ * one call per burst gives the 802.x classes, the verdicts and what FragSumVerify needs where the
+ * stack's reassembly completes; a stack that never reassembles needs RxBurstEtherHost only.
+ *
  * EtherClass / RxBurstEtherTally: host logic, no device work. EtherClass is the rules on one frame in
  * host memory (*p_hdr_len, optional: 14 / 22, 0 for the INV_* classes); the tally's rules are
  * RxBurstTally's: ctr[c] += frames of class c; NULL with n_frame != 0 NET_ERR_FAULT_NULL_PTR, a class
@@ -575,7 +603,22 @@ NET_ERR  NetUtil_MI355X_RxBurstEther       (const void      *d_base,
                                             uint8_t         *d_l2,
                                             void            *hip_stream);
 
-uint8_t  NetUtil_MI355X_EtherClass         (const void      *frame,
+NET_ERR  NetUtil_MI355X_RxBurstEtherSums   (const void      *d_base,
+                                            const uint64_t  *d_off,
+                                            const uint16_t  *d_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
+                                            uint32_t         rx_cfg,
+                                            uint32_t         eth_cfg,
+                                            const uint8_t   *hw_addr,
+                                            uint8_t         *d_action,
+                                            uint8_t         *d_flags,
+                                            uint8_t         *d_l2,
+                                            NETCSUM_FRAG_SUM *d_sums,
+                                            void            *hip_stream);
+
+uint8_t  NetUtil_MI355X_EtherClass        (const void      *frame,
                                             uint16_t         len,
                                             uint32_t         eth_cfg,
                                             const uint8_t   *hw_addr,
@@ -703,7 +746,9 @@ NET_ERR  NetUtil_MI355X_RxBurstHost        (const void      *h_base,
                                             uint8_t         *h_flags,
                                             uint32_t         n_chunks);
 
-/* RxBurstHost with the fragment payload sums of (2b'''); always the copy pipeline. */
+/* RxBurstHost with the fragment payload sums of (2b'''): in place from a pinned ring by the resident
+ * burst server under RxBurstHost's conditions with NETCSUM_TUNE_BURST_ZERO_COPY 3 (LastLaunch():
+ * "burst_server_kernel rx,sums form=<form> pkts_per_wave=<K> zero-copy"), else the copy pipeline. */
 NET_ERR  NetUtil_MI355X_RxBurstSumsHost    (const void      *h_base,
                                             const uint64_t  *h_off,
                                             const uint16_t  *h_len,
@@ -741,6 +786,27 @@ NET_ERR  NetUtil_MI355X_RxBurstEtherHost   (const void      *h_base,
                                             uint8_t         *h_action,
                                             uint8_t         *h_flags,
                                             uint8_t         *h_l2,
+                                            uint32_t         n_chunks);
+
+/* RxBurstEtherSums ((2b'''') above) over frames in host memory: RxBurstEtherHost with h_sums after h_l2.
+ * In place under RxBurstEtherHost's conditions, the records arriving in coherent pinned memory behind a
+ * sentinel of their own (0xFFFFFFFF: no fragment payload has 65 535 octets); NetUtil_MI355X_LastLaunch()
+ * then reads "ether_demux b=<server blocks> | burst_server_kernel rx,sums form=ether pkts_per_wave=<K>
+ * zero-copy". Every other call takes the copy pipeline (the records: 4 B more per frame D2H). The same
+ * bytes either way. */
+NET_ERR  NetUtil_MI355X_RxBurstEtherSumsHost(const void     *h_base,
+                                            const uint64_t  *h_off,
+                                            const uint16_t  *h_len,
+                                            uint64_t         stride,
+                                            CPU_INT16U       frame_len,
+                                            uint32_t         n_frame,
+                                            uint32_t         rx_cfg,
+                                            uint32_t         eth_cfg,
+                                            const uint8_t   *hw_addr,
+                                            uint8_t         *h_action,
+                                            uint8_t         *h_flags,
+                                            uint8_t         *h_l2,
+                                            NETCSUM_FRAG_SUM *h_sums,
                                             uint32_t         n_chunks);
 
 /* TxBurstEther ((2b''''') above) over frames in host memory — the driver's Tx ring itself; h_off == NULL

@@ -21,7 +21,8 @@
  *                      pipeline)
  * and a check that every Rx action is DELIVER and every frame's class ETHER_IPV4. One JSON line per n on
  * stdout. With the argument "txether": the Tx Ether mode (tx_ether_only below), TxBurstEtherHost on the
- * same slots against TxBurstHost at +14.
+ * same slots against TxBurstHost at +14. With "ethersums" (and optionally "frag"): the fragment-sums mode
+ * (ether_sums_only below), RxBurstEtherSumsHost against RxBurstEtherHost and RxBurstSumsHost on the same ring.
  *
  * Built here (the binary travels with the tree; tools/build/ is git-ignored), run on the GPU box:
  *   gcc -O2 -std=c11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tools/burst_latency.c \
@@ -116,9 +117,10 @@ static void build(uint8_t *slot)
     tcp[16] = tcp[17] = 0;
 }
 
-typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST, RX_ETHER_HOST, TX_ETHER_HOST } kind_t;
+typedef enum { RX_DEV, TX_DEV, RX_HOST, TX_HOST, RX_ETHER_HOST, TX_ETHER_HOST, RX_ETHER_SUMS_HOST, RX_SUMS_HOST } kind_t;
 
 static uint8_t *g_dring, *g_hring, *g_dact, *g_hact, *g_hl2;
+static NETCSUM_FRAG_SUM *g_hsums;
 static uint16_t *g_hlen;                                        /* received lengths: FRAME each */
 static hipStream_t g_st;
 
@@ -147,6 +149,13 @@ static void call(kind_t k, uint32_t n)
         break;
     case TX_ETHER_HOST:
         NET_OK(NetUtil_MI355X_TxBurstEtherHost(g_hring, NULL, g_hlen, SLOT, 0, n, NULL, g_hl2, chunks));
+        break;
+    case RX_ETHER_SUMS_HOST:
+        NET_OK(NetUtil_MI355X_RxBurstEtherSumsHost(g_hring, NULL, g_hlen, SLOT, 0, n, 0u, 0u, NULL, g_hact, NULL, g_hl2, g_hsums,
+                                                   chunks));
+        break;
+    case RX_SUMS_HOST:
+        NET_OK(NetUtil_MI355X_RxBurstSumsHost(g_hring + IP_AT, NULL, NULL, SLOT, DGRAM, n, 0u, g_hact, NULL, g_hsums, chunks));
         break;
     }
 }
@@ -254,6 +263,90 @@ static int tx_ether_only(void)
     return ok ? 0 : 1;
 }
 
+/* "ethersums" [frag]: the fragment-sums mode. Bursts of 1 / 64 / 1024 frames of 1514 octets from the pinned ring
+ * of 1520-B slots, n_chunks 0; with "frag" every fourth frame, the first included, is an IPv4 fragment (More Fragments set, the
+ * header checksum made right again), else none is. The first line is taken before the thread's first sums
+ * burst, i.e. from the server instantiation without sums (RxBurstEtherHost and RxBurstHost at +14). Then three
+ * interleaved repetitions, on the server with sums, of RxBurstEtherSumsHost (ether_sums_host_auto), RxBurstEtherHost
+ * (ether_host_auto), RxBurstSumsHost at +14 (sums_host_auto), and the two sums calls under
+ * NETCSUM_TUNE_BURST_ZERO_COPY 0, the copy pipeline (_copy). Medians of REPS calls; every result is checked:
+ * class ETHER_IPV4, a fragment DELIVER_L4_UNVERIFIED with a record of 1480 octets and a non-zero sum, every
+ * other frame DELIVER with the record {0, 0}. */
+static void make_fragment(uint8_t *slot)
+{
+    uint8_t *ip = slot + IP_AT;
+    uint32_t sum = 0, i;
+    ip[6] = 0x20;                                               /* More Fragments, offset 0 */
+    ip[10] = ip[11] = 0;
+    for (i = 0; i < 20u; i += 2u) sum += ((uint32_t)ip[i] << 8) | ip[i + 1u];
+    while (sum >> 16) sum = (sum & 0xFFFFu) + (sum >> 16);
+    sum = ~sum & 0xFFFFu;
+    ip[10] = (uint8_t)(sum >> 8);
+    ip[11] = (uint8_t)sum;
+}
+
+static int sums_ok(uint32_t n, int frag, int ether, int sums)
+{
+    int ok = 1;
+    uint32_t i;
+    for (i = 0; i < n; ++i) {
+        const int f = frag && (i & 3u) == 0u;
+        ok &= g_hact[i] == (f ? NETCSUM_RX_DELIVER_L4_UNVERIFIED : NETCSUM_RX_DELIVER);
+        if (ether) ok &= g_hl2[i] == NETCSUM_L2_ETHER_IPV4;
+        if (sums) ok &= f ? (g_hsums[i].len == DGRAM - 20u && g_hsums[i].sum != 0u) : (g_hsums[i].len == 0u && g_hsums[i].sum == 0u);
+    }
+    return ok;
+}
+
+static double timed_checked(kind_t k, uint32_t n, int frag, int *ok)
+{
+    double t;
+    const int ether = k != RX_HOST && k != RX_SUMS_HOST, sums = k == RX_ETHER_SUMS_HOST || k == RX_SUMS_HOST;
+    memset(g_hact, 0xEE, n);
+    memset(g_hl2, 0xEE, n);
+    memset(g_hsums, 0x5A, (size_t)n * sizeof *g_hsums);
+    t = time_us(k, n);
+    *ok &= sums_ok(n, frag, ether, sums);
+    return t;
+}
+
+static int ether_sums_only(int frag)
+{
+    static const uint32_t sizes[] = {1u, 64u, 1024u};
+    int rep, ok = 1;
+    uint32_t s, i;
+    g_chunks = 0u;
+    if (frag) {
+        for (i = 0u; i < 4096u; i += 4u) make_fragment(g_hring + (size_t)i * SLOT);
+    }
+    printf("{\"phase\": \"before_sums\", \"fragments\": %s", frag ? "true" : "false");
+    for (s = 0; s < 3; ++s) {
+        const uint32_t n = sizes[s];
+        printf(", \"ether_host_auto_%u_us\": %.2f", n, timed_checked(RX_ETHER_HOST, n, frag, &ok));
+        printf(", \"rx_host_auto_%u_us\": %.2f", n, timed_checked(RX_HOST, n, frag, &ok));
+    }
+    printf(", \"all_right\": %s}\n", ok ? "true" : "false");
+    fflush(stdout);
+    for (rep = 0; rep < 3 && ok; ++rep) {
+        printf("{\"rep\": %d, \"fragments\": %s", rep, frag ? "true" : "false");
+        for (s = 0; s < 3; ++s) {
+            const uint32_t n = sizes[s];
+            printf(", \"ether_sums_host_auto_%u_us\": %.2f", n, timed_checked(RX_ETHER_SUMS_HOST, n, frag, &ok));
+            printf(", \"ether_host_auto_%u_us\": %.2f", n, timed_checked(RX_ETHER_HOST, n, frag, &ok));
+            printf(", \"sums_host_auto_%u_us\": %.2f", n, timed_checked(RX_SUMS_HOST, n, frag, &ok));
+            printf(", \"rx_host_auto_%u_us\": %.2f", n, timed_checked(RX_HOST, n, frag, &ok));
+            NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, 0));
+            printf(", \"ether_sums_host_auto_copy_%u_us\": %.2f", n, timed_checked(RX_ETHER_SUMS_HOST, n, frag, &ok));
+            printf(", \"sums_host_auto_copy_%u_us\": %.2f", n, timed_checked(RX_SUMS_HOST, n, frag, &ok));
+            NET_OK(NetUtil_MI355X_Tune(NETCSUM_TUNE_BURST_ZERO_COPY, 3));
+        }
+        printf(", \"all_right\": %s}\n", ok ? "true" : "false");
+        fflush(stdout);
+    }
+    NetUtil_MI355X_ThreadRelease();
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     static const uint32_t sizes[] = {1u, 10u, 16u, 32u, 64u, 128u, 256u, 1024u, 4096u, 16384u, 65536u, 262144u};
@@ -266,6 +359,7 @@ int main(int argc, char **argv)
     HIP_OK(hipHostMalloc((void **)&g_hring, bytes, 0));
     HIP_OK(hipHostMalloc((void **)&g_hact, NMAX, 0));
     HIP_OK(hipHostMalloc((void **)&g_hl2, NMAX, 0));
+    HIP_OK(hipHostMalloc((void **)&g_hsums, 4096u * sizeof *g_hsums, 0));
     g_hlen = malloc(NMAX * sizeof *g_hlen);
     if (g_hlen == NULL) return 2;
     for (i = 0; i < NMAX; ++i) g_hlen[i] = FRAME;
@@ -274,6 +368,7 @@ int main(int argc, char **argv)
     HIP_OK(hipMemcpy(g_dring, g_hring, bytes, hipMemcpyHostToDevice));
     if (argc > 1 && strcmp(argv[1], "zc") == 0) return zc_only();
     if (argc > 1 && strcmp(argv[1], "txether") == 0) return tx_ether_only();
+    if (argc > 1 && strcmp(argv[1], "ethersums") == 0) return ether_sums_only(argc > 2 && strcmp(argv[2], "frag") == 0);
     for (s = 0; s < sizeof sizes / sizeof sizes[0]; ++s) {
         const uint32_t n = sizes[s];
         double rx_dev, tx_dev, rx_host, tx_host;

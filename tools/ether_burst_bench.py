@@ -17,7 +17,11 @@ One JSON line per pass (median of 20 launches per figure after a timed warm-up, 
 
   python tools/ether_burst_bench.py [--frames N] [--passes K] >> profiles/ether_burst_bench.jsonl
 
-Every pass also checks the results it timed: all three calls' actions, and the classes.
+With --sums a fourth call alternates with them: `ether_sums`, RxBurstEtherSums on the same ring (the
+same two launches with the SUMS instantiation of the packet pass and 4 B more written per frame; no frame
+of this ring is a fragment, so every record is {0, 0}); ether_sums - ether is what the records cost.
+
+Every pass also checks the results it timed: all the calls' actions, the classes, and the records.
 """
 import argparse
 import json
@@ -68,6 +72,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=1 << 20)
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--sums", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -83,6 +88,12 @@ def main():
     def ether():
         netcsum.rx_burst_ether(r0, n, act_e, l2, lens=lens, stride=STRIDE, hw_addr=HW, stream=st)
 
+    act_es, l2s = (torch.full((n,), 0xEE, dtype=torch.uint8, device=dev) for _ in range(2))
+    rec = torch.full((n if a.sums else 1,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+
+    def ether_sums():
+        netcsum.rx_burst_ether_sums(r0, n, act_es, l2s, rec, lens=lens, stride=STRIDE, hw_addr=HW, stream=st)
+
     def strided():
         netcsum.rx_burst(r0[HDR:], n, act_s, stride=STRIDE, pkt_len=TOT, stream=st)
 
@@ -91,12 +102,17 @@ def main():
 
     for p in range(a.passes):
         r = {"pass": p, "frames": n, "stride": STRIDE, "frame_bytes": FRAME}
-        for name, fn in (("ether", ether), ("strided", strided), ("offlen", offlen)):
+        calls = (("ether", ether), ("strided", strided), ("offlen", offlen)) + ((("ether_sums", ether_sums),) if a.sums else ())
+        for name, fn in calls:
             r[f"{name}_ms"] = events_ms(fn, st)
             r[f"kernel_{name}"] = netcsum.last_launch()
         torch.cuda.synchronize()
         ok = all(bool((x == netcsum.RX_DELIVER).all()) for x in (act_e, act_s, act_o))
         ok = ok and bool((l2 == netcsum.L2_ETHER_IPV4).all())
+        if a.sums:
+            ok = ok and bool((act_es == netcsum.RX_DELIVER).all()) and bool((l2s == netcsum.L2_ETHER_IPV4).all())
+            ok = ok and bool((rec == 0).all())
+            r["ether_sums_minus_ether_ms"] = r["ether_sums_ms"] - r["ether_ms"]
         r["ether_minus_strided_ms"] = r["ether_ms"] - r["strided_ms"]          # frame-level input, all of it
         r["ether_minus_offlen_ms"] = r["ether_ms"] - r["offlen_ms"]            # the demux pass alone
         r["ether_over_strided"] = round(r["ether_ms"] / r["strided_ms"], 4)

@@ -835,10 +835,15 @@ NET_ERR NetUtil_MI355X_RxBurstSums(const void* d_base, const uint64_t* d_off, co
 // walk pass), which fits below the descriptors, so its lease never grows the buffer under them. Under
 // stream capture the rule is the Tx records': the slot is pinned, and a capture needs one uncaptured
 // call of at least its size first.
-NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
-                                    CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
-                                    const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
-                                    void* hip_stream) {
+// d_sums (RxBurstEtherSums; checked by the entry point): the packet batch is RxBurstSums' — the SUMS
+// instantiations of the same launch. It leases what RxBurst's does and nothing more: its deferred-run list is
+// the same list, and a datagram that waits for the walk is marked in d_sums itself (kFragSumWalk), not in
+// scratch; the lane-group form's own flags (one byte per frame) are the other case, below 4 B per frame too.
+// So the descriptors lie above all of it, as they do without sums (pkt_batch's layouts: 256 + 4 n + 16 at most).
+static NET_ERR rx_burst_ether(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                              CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                              const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
+                              NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
     if (n_frame != 0 && (d_action == nullptr || d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
     if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
     if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
@@ -873,6 +878,7 @@ NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, c
     PktJob j = pkt_job(d_base, a.off_out, a.len_out, 0, 0, n_frame, d_flags, hip_stream);
     j.action = d_action;
     j.rx_cfg = rx_cfg;
+    j.sums = d_sums;
     const NET_ERR e = pkt_batch(tls_tune, j);
     if (e != NET_UTIL_ERR_NONE) return e;
     NC_HIP(scratch.end());
@@ -880,6 +886,29 @@ NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, c
     snprintf(desc, sizeof desc, "ether_demux b=%u | %.220s", netcsum::ether_demux_blocks(n_frame), netcsum::last_launch());
     netcsum::set_last_launch(desc);
     return NET_UTIL_ERR_NONE;
+}
+
+NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                                    CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                    const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
+                                    void* hip_stream) {
+    return rx_burst_ether(d_base, d_off, d_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, d_action, d_flags, d_l2,
+                          nullptr, hip_stream);
+}
+
+// RxBurstEther's checks in their order, then d_sums' (RxBurstSums'); n_frame 0 succeeds without a launch.
+NET_ERR NetUtil_MI355X_RxBurstEtherSums(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                                        CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                        const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
+                                        NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
+    if (n_frame != 0 && (d_action == nullptr || d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame != 0 && d_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    if (((uintptr_t)d_sums & 3u) != 0u || n_frame > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    return rx_burst_ether(d_base, d_off, d_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, d_action, d_flags, d_l2,
+                          d_sums, hip_stream);
 }
 
 // Tx burst of Ethernet frames: the Tx demux pass (netcsum_ether.hip ether_tx_demux_kernel) writes each

@@ -58,6 +58,8 @@ struct HostCtx {
     // burst number posted
     hipStream_t          sstream = nullptr;
     bool                 server_live = false;
+    bool                 want_sums = false;       // a sums burst was posted: every launch from then on is the
+                                                  // server's SUMS instantiation (burst_server_run)
     uint64_t             post_seq = 0;
 
     bool empty() const {
@@ -458,7 +460,9 @@ constexpr uint64_t kBurstZCSpan = 64ull << 20;          // ring bytes the kernel
 constexpr size_t kBurstWord = 0, kBurstPost = 64, kBurstClosed = 128, kBurstFlags = 256, kBurstAct = kBurstFlags + kBurstZC,
                  kBurstOff = kBurstAct + kBurstZC, kBurstLen = kBurstOff + 8u * kBurstZC,
                  kBurstRec = kBurstLen + 2u * kBurstZC, kBurstL2 = kBurstRec + 8u * kBurstZC,
-                 kBurstHostBytes = kBurstL2 + kBurstZC;
+                 kBurstSums = kBurstL2 + kBurstZC, kBurstHostBytes = kBurstSums + 4u * kBurstZC;
+// (kBurstSums: one NETCSUM_FRAG_SUM per frame, sentinel 0xFFFFFFFF — no fragment payload has 65 535 octets:
+// IPv4 at most 65 515, IPv6 at most 65 527 after the Fragment header; {0, 0} is a real record)
 // device side: [flags | actions | Tx records]
 constexpr size_t kBurstDevRec = 2u * kBurstZC, kBurstDevBytes = kBurstDevRec + 8u * kBurstZC;
 
@@ -531,7 +535,8 @@ static NET_ERR launch_server(const Tune& t, HostCtx& c, uint64_t seq0) {
     a.seq0 = seq0;
     a.idle_ticks = (uint64_t)std::max(1, t.burst_idle) * (uint64_t)std::max(khz, 1) / 1000u;
     a.life_ticks = (uint64_t)std::max(1, t.burst_life) * (uint64_t)std::max(khz, 1) / 1000u;
-    NC_HIP(netcsum::launch_burst_server(a, kServerBlocks, c.sstream));
+    NC_HIP(netcsum::launch_burst_server(a, kServerBlocks, c.sstream,
+                                        c.want_sums ? reinterpret_cast<uint32_t*>(c.h_burst_dev + kBurstSums) : nullptr));
     c.server_live = true;
     return NET_UTIL_ERR_NONE;
 }
@@ -588,6 +593,14 @@ static NET_ERR burst_server_run(const Tune& t, HostCtx& c, netcsum::BurstPost p,
         c.server_live = false;
         return all_ready(from) ? NET_UTIL_ERR_NONE : launch_server(t, c, p.seq - 1u);
     };
+    // A post with fragment sums goes to the SUMS instantiation only. The thread's server is the other one
+    // until its first such burst: that one is stopped and waited out here, before the post (it must never
+    // read it), and every launch from then on is the SUMS one, which serves posts of both kinds — a driver
+    // that alternates relaunches nothing.
+    if (((p.form >> 1) & netcsum::kBurstSums) != 0u && !c.want_sums) {
+        c.want_sums = true;
+        if (c.server_live && !c.stop_server(2000)) return dev_fail("burst server still queued or running", hipErrorNotReady);
+    }
     p.seq = ++c.post_seq;
     p.check = netcsum::burst_post_check(p);
     write_post(c, p);
@@ -629,11 +642,15 @@ static NET_ERR burst_server_run(const Tune& t, HostCtx& c, netcsum::BurstPost p,
 // zero-copy path, not the copy pipeline, was taken)
 // (an Ether burst: "ether_demux b=<blocks> | " — Tx: "ether_tx_demux b=<blocks> | " — in front, the
 // device forms' shape, with the server's blocks, whose waves did the demux)
+// (a burst with fragment sums: ",sums" after the direction — "burst_server_kernel rx,sums form=…")
 static void server_launch_name(uint32_t form, uint32_t spw, bool tx) {
     char d[128];
     const bool ether = (form & netcsum::kBurstKindMask) == netcsum::kBurstEther;
+    const bool sums = (form & netcsum::kBurstSums) != 0u;
+    form &= ~netcsum::kBurstSums;
     int k = ether ? snprintf(d, sizeof d, "%s b=%d | ", tx ? "ether_tx_demux" : "ether_demux", kServerBlocks) : 0;
-    snprintf(d + k, sizeof d - (size_t)k, "burst_server_kernel %s form=%s pkts_per_wave=%u zero-copy", tx ? "tx" : "rx",
+    snprintf(d + k, sizeof d - (size_t)k, "burst_server_kernel %s%s form=%s pkts_per_wave=%u zero-copy", tx ? "tx" : "rx",
+             sums ? ",sums" : "",
              ether ? "ether" : form == netcsum::kBurstWhole ? "whole" : form == netcsum::kBurstLive ? "live" : "offlen", spw);
     netcsum::set_last_launch(d);
 }
@@ -710,6 +727,7 @@ static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t
         post.n = j.n;
         post.pkt_len = j.pkt_len;
         post.spw = spw;
+        if (!j.tx && j.sums != nullptr) form |= netcsum::kBurstSums;   // (the records: the caller's sentinel and wait)
         post.form = (form << 1) | (j.tx ? 1u : 0u);
         server_launch_name(form, spw, j.tx);
         return burst_server_run(t, c, post, ready, j.n);
@@ -742,7 +760,19 @@ static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t
 }  // extern "C++"
 
 // Rx over a pinned ring in place; *taken as burst_job's.
+// With fragment sums (h.sums, RxBurstSumsHost): by the resident server only — TUNE_BURST_ZERO_COPY 3 and a
+// layout the server takes (server_form); the launch-per-burst modes' kernels write a record twice where a
+// datagram waits for the walk (kFragSumWalk), which a polled sentinel cannot tell from the result. The
+// records arrive behind a sentinel of their own (0xFFFFFFFF, kBurstSums).
 static NET_ERR rx_burst_zero_copy(const Tune& t, HostCtx& c, const PktJob& h, bool* taken) {
+    *taken = false;
+    NETCSUM_FRAG_SUM* h_sums = h.sums;
+    if (h_sums != nullptr) {
+        uint32_t form = 0, spw = 0;
+        if (t.burst_zc != 3 || h.n > kBurstZC || !server_form(h.off, h.stride, h.pkt_len, h.n, &form, &spw)) {
+            return NET_UTIL_ERR_NONE;
+        }
+    }
     PktJob j;
     NET_ERR e = burst_job(c, h, &j, taken);
     if (e != NET_UTIL_ERR_NONE || !*taken) return e;
@@ -750,13 +780,26 @@ static NET_ERR rx_burst_zero_copy(const Tune& t, HostCtx& c, const PktJob& h, bo
     post.rx_cfg = h.rx_cfg;
     const uint8_t* hf = c.h_burst + kBurstFlags;
     const uint8_t* ha = c.h_burst + kBurstAct;
-    e = burst_deliver(t, c, j, h.off, post, BurstOut{{kBurstFlags, kBurstAct}, {0u, kBurstZC}, h.n, h.action != nullptr},
-                      [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                               *(volatile const uint8_t*)(ha + i) != 0xFFu; },
-                      [](PktJob& q, uint8_t* r0, uint8_t* r1) { q.flags = r0; q.action = r1; });
+    const uint8_t* hs = c.h_burst + kBurstSums;
+    const BurstOut out{{kBurstFlags, kBurstAct}, {0u, kBurstZC}, h.n, h.action != nullptr};
+    auto point = [](PktJob& q, uint8_t* r0, uint8_t* r1) { q.flags = r0; q.action = r1; };
+    if (h_sums != nullptr) {
+        std::memset(c.h_burst + kBurstSums, 0xFF, (size_t)h.n * 4u);
+        e = burst_deliver(t, c, j, h.off, post, out,
+                          [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
+                                                   *(volatile const uint8_t*)(ha + i) != 0xFFu &&
+                                                   *(volatile const uint32_t*)(hs + 4u * i) != 0xFFFFFFFFu; },
+                          point);
+    } else {
+        e = burst_deliver(t, c, j, h.off, post, out,
+                          [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
+                                                   *(volatile const uint8_t*)(ha + i) != 0xFFu; },
+                          point);
+    }
     if (e != NET_UTIL_ERR_NONE) return e;
     if (h.flags) std::memcpy(h.flags, hf, h.n);
     if (h.action) std::memcpy(h.action, ha, h.n);
+    if (h_sums) std::memcpy(h_sums, hs, (size_t)h.n * 4u);
     return NET_UTIL_ERR_NONE;
 }
 
@@ -972,8 +1015,7 @@ static NET_ERR pkt_host(const PktJob& h, uint32_t n_chunks) {
         return NET_ERR_FAULT_NULL_PTR;
     }
     const Tune& t = tune();
-    // (a burst with fragment sums always takes the copy pipeline: the resident server has no such output)
-    if (n_chunks == 0 && t.burst_zc != 0 && h.sums == nullptr) {   // a burst from a pinned ring: in place
+    if (n_chunks == 0 && t.burst_zc != 0) {                  // a burst from a pinned ring: in place
         HostCtx* cp = nullptr;
         NET_ERR e = host_ctx(&cp);
         if (e != NET_UTIL_ERR_NONE) return e;
@@ -1044,10 +1086,12 @@ static void ether_span(const uint64_t* h_off, const uint16_t* h_len, uint64_t st
 // rx_burst_zero_copy's conditions — at most kBurstZC frames whose span is one pinned allocation of at
 // most kBurstZCSpan bytes — and in the server's mode only (TUNE_BURST_ZERO_COPY 3: the launch-per-burst
 // experiments are not extended to frames). *taken = false: the caller takes the copy pipeline.
+// h_sums (RxBurstEtherSumsHost): the post carries kBurstSums, and the frames' records arrive behind their own
+// sentinel (0xFFFFFFFF, kBurstSums) and are polled with the rest.
 static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h_base, const uint64_t* h_off,
                                         const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t n,
                                         uint32_t rx_cfg, uint32_t eth_cfg, const uint8_t* hw_addr, uint8_t* h_action,
-                                        uint8_t* h_flags, uint8_t* h_l2, bool* taken) {
+                                        uint8_t* h_flags, uint8_t* h_l2, NETCSUM_FRAG_SUM* h_sums, bool* taken) {
     *taken = false;
     if (n > kBurstZC) return NET_UTIL_ERR_NONE;
     uint64_t lo = 0, hi = 0;
@@ -1071,9 +1115,14 @@ static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h
     uint8_t* hf = c.h_burst + kBurstFlags;
     uint8_t* ha = c.h_burst + kBurstAct;
     uint8_t* hl = c.h_burst + kBurstL2;
+    uint8_t* hs = c.h_burst + kBurstSums;
     std::memset(hf, 0xFF, n);
     std::memset(ha, 0xFF, n);
     std::memset(hl, 0xFF, n);
+    if (h_sums) {
+        std::memset(hs, 0xFF, (size_t)n * 4u);
+        form |= netcsum::kBurstSums;
+    }
     netcsum::BurstPost post{};
     post.ring = reinterpret_cast<uint64_t>(d_lo - lo);      // the base's alias: offsets count from it
     post.stride = (uint32_t)stride;
@@ -1089,13 +1138,21 @@ static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h
         post.hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
     }
     server_launch_name(form, spw, false);
-    e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                                              *(volatile const uint8_t*)(ha + i) != 0xFFu &&
-                                                              *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
+    if (h_sums) {
+        e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
+                                                                  *(volatile const uint8_t*)(ha + i) != 0xFFu &&
+                                                                  *(volatile const uint8_t*)(hl + i) != 0xFFu &&
+                                                                  *(volatile const uint32_t*)(hs + 4u * i) != 0xFFFFFFFFu; }, n);
+    } else {
+        e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
+                                                                  *(volatile const uint8_t*)(ha + i) != 0xFFu &&
+                                                                  *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
+    }
     if (e != NET_UTIL_ERR_NONE) return e;
     if (h_flags) std::memcpy(h_flags, hf, n);
     std::memcpy(h_action, ha, n);
     std::memcpy(h_l2, hl, n);
+    if (h_sums) std::memcpy(h_sums, hs, (size_t)n * 4u);
     return NET_UTIL_ERR_NONE;
 }
 
@@ -1105,10 +1162,12 @@ static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h
 // descriptors (per-frame lengths also without offsets: a ring of slots) and the classes as a third
 // result. Per chunk: H2D of the frames' span and descriptors, the device form (demux, packet batch) on
 // the chunk's stream, D2H of actions, flags and classes.
-NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
-                                        CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
-                                        const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
-                                        uint32_t n_chunks) {
+// h_sums (RxBurstEtherSumsHost; the entry point has checked it): both stages also return one NETCSUM_FRAG_SUM
+// per frame — the copy pipeline through a fourth result region and the device form RxBurstEtherSums.
+static NET_ERR rx_burst_ether_host(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                   CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                   const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
+                                   NETCSUM_FRAG_SUM* h_sums, uint32_t n_chunks) {
     if (n_frame != 0 && (h_action == nullptr || h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
     if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
     if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
@@ -1122,7 +1181,7 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
     if (n_chunks == 0 && t.burst_zc == 3) {                  // a burst from a pinned ring: in place
         bool taken = false;
         e = rx_burst_ether_zero_copy(t, c, h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr,
-                                     h_action, h_flags, h_l2, &taken);
+                                     h_action, h_flags, h_l2, h_sums, &taken);
         if (taken) return e;
     }
     std::vector<HostChunk> ch;
@@ -1135,11 +1194,14 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
         }
     }
     const uint32_t per = ch[0].ns;
-    // device slot: [bytes | offsets | lengths | flags | actions | classes]; host slot: [offsets | lengths]
+    // device slot: [bytes | offsets | lengths | flags | actions | classes | fragment sums]; host slot:
+    // [offsets | lengths]
     const size_t o_off = al256(maxb), o_len = o_off + al256(h_off ? (size_t)per * 8u : 0u);
     const size_t o_fl = o_len + al256(h_len ? (size_t)per * 2u : 0u), o_act = o_fl + al256(per), o_l2 = o_act + al256(per);
+    const size_t o_sum = o_l2 + al256(per);
     const size_t hs_len = al256(h_off ? (size_t)per * 8u : 0u);
-    e = ensure_pipe(c, o_l2 + al256(per), hs_len + al256(h_len ? (size_t)per * 2u : 0u));
+    e = ensure_pipe(c, o_sum + al256(h_sums ? (size_t)per * sizeof(NETCSUM_FRAG_SUM) : 0u),
+                    hs_len + al256(h_len ? (size_t)per * 2u : 0u));
     if (e != NET_UTIL_ERR_NONE) return e;
     PipeDrainOnExit guard{c};
     const uint8_t* hb = static_cast<const uint8_t*>(h_base);
@@ -1160,17 +1222,50 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
             std::memcpy(h_l, h_len + q.s0, (size_t)q.ns * 2u);
             NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
         }
-        e = NetUtil_MI355X_RxBurstEther(d, h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr,
-                                        h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr, stride, frame_len, q.ns,
-                                        rx_cfg, eth_cfg, hw_addr, d + o_act, h_flags ? d + o_fl : nullptr, d + o_l2, st);
+        const uint64_t* d_o = h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr;
+        const uint16_t* d_l = h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr;
+        if (h_sums) {
+            e = NetUtil_MI355X_RxBurstEtherSums(d, d_o, d_l, stride, frame_len, q.ns, rx_cfg, eth_cfg, hw_addr, d + o_act,
+                                                h_flags ? d + o_fl : nullptr, d + o_l2,
+                                                reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum), st);
+        } else {
+            e = NetUtil_MI355X_RxBurstEther(d, d_o, d_l, stride, frame_len, q.ns, rx_cfg, eth_cfg, hw_addr, d + o_act,
+                                            h_flags ? d + o_fl : nullptr, d + o_l2, st);
+        }
         if (e != NET_UTIL_ERR_NONE) return e;
         if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
         NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, st));
         NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
+        if (h_sums) {
+            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, st));
+        }
     }
     for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
     guard.done = true;
     return NET_UTIL_ERR_NONE;
+}
+
+NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                        CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                        const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
+                                        uint32_t n_chunks) {
+    return rx_burst_ether_host(h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, h_action, h_flags,
+                               h_l2, nullptr, n_chunks);
+}
+
+// RxBurstEtherHost's checks in their order, then the records' (RxBurstSumsHost's).
+NET_ERR NetUtil_MI355X_RxBurstEtherSumsHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
+                                            CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
+                                            const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
+                                            NETCSUM_FRAG_SUM* h_sums, uint32_t n_chunks) {
+    if (n_frame != 0 && (h_action == nullptr || h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame != 0 && h_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    if (((uintptr_t)h_sums & 3u) != 0u || n_frame > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (n_frame == 0) return NET_UTIL_ERR_NONE;
+    return rx_burst_ether_host(h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, h_action, h_flags,
+                               h_l2, h_sums, n_chunks);
 }
 
 static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,

@@ -257,7 +257,8 @@ struct alignas(64) BurstPost {
     uint32_t pkt_len;      // strided forms: bytes present per slot
     uint32_t spw;          // frames per wave run
     uint32_t form;         // bit 0 Tx; form >> 1: kBurstWhole / kBurstLive / kBurstOffLen, or kBurstEther
-                           // with kBurstEtherOff / kBurstEtherLen for the descriptors that are staged
+                           // with kBurstEtherOff / kBurstEtherLen for the descriptors that are staged;
+                           // kBurstSums (Rx): one NETCSUM_FRAG_SUM per frame as well
     uint32_t udp_mode;     // Tx: PktBatchArgs::udp_tx_csum
     uint32_t rx_cfg;       // Rx: NETCSUM_RXCFG_* for the actions
     uint32_t check;        // burst_post_check of every other field: a read that tore the line fails it
@@ -274,6 +275,11 @@ constexpr uint32_t kBurstWhole = 0u, kBurstLive = 1u, kBurstOffLen = 2u;
 // (netcsum_etherhead.h) and streams their datagrams from descriptors it keeps in registers. Frame starts
 // are off[i] with kBurstEtherOff, else i * stride; received lengths len[i] with kBurstEtherLen, else pkt_len.
 constexpr uint32_t kBurstEther = 3u, kBurstKindMask = 3u, kBurstEtherOff = 4u, kBurstEtherLen = 8u;
+// Rx bursts with fragment payload sums (RxBurstSumsHost, RxBurstEtherSumsHost): a bit of the form beside
+// the kind (the line has no spare dword; the check covers it with the form), posted only to the server's
+// SUMS instantiation, whose waves run the SUMS forms of the same runs and store one record per frame
+// (BurstServerSumsArgs::sums) beside its flag and action.
+constexpr uint32_t kBurstSums = 16u;
 constexpr int kBurstServerMaxBlocks = 16;
 __host__ __device__ __forceinline__ uint32_t burst_post_check(const BurstPost& p) {
     const uint32_t d[15] = {(uint32_t)p.seq, (uint32_t)(p.seq >> 32), (uint32_t)p.ring, (uint32_t)(p.ring >> 32),
@@ -298,8 +304,16 @@ struct BurstServerArgs {
                                       // even while bursts keep coming (bounds how long the server holds
                                       // the hardware queue its stream shares with other streams)
 };
-// blocks x 256 threads on stream s (a stream of its own: the kernel runs until it is idle)
-hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t s);
+// The SUMS instantiation's arguments (a type of its own: the other instantiation's argument block, which
+// it keeps in scratch for the leader's wait, stays as it was).
+struct BurstServerSumsArgs : BurstServerArgs {
+    uint32_t*           sums;      // kBurstSums: the frames' NETCSUM_FRAG_SUM records, sum | len << 16
+};
+// blocks x 256 threads on stream s (a stream of its own: the kernel runs until it is idle). sums (the
+// records' device alias) non-null: the instantiation that also serves kBurstSums posts. A thread's server
+// is the other one until the thread first asks for sums: that one's code and resources are those of a
+// server without the feature.
+hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t s, uint32_t* sums = nullptr);
 
 // ---- netcsum_v6walk.hip
 // IPv6 extension-header chains past the batch kernels' window (flags EXT_HDR): walked to the end and

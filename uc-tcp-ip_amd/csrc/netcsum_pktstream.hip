@@ -37,6 +37,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/netcsum_mi355x.h"
 #include "netcsum_device.h"
@@ -620,7 +621,7 @@ __device__ __forceinline__ void pkt_run(const PktBatchArgs& A, PktTxRecord* rec,
     if constexpr (kWalkHere) {
         if (walk_here) {
             if constexpr (REGS) {
-                v6walk::walk_wave_regs<TX>(A, s_begin, need, lane, O + prel, avail);
+                v6walk::walk_wave_regs<TX, SUMS>(A, s_begin, need, lane, O + prel, avail);
             } else {
                 v6walk::walk_wave<TX, SUMS>(A, s_begin, need, lane);
             }
@@ -723,7 +724,9 @@ struct EtherRunArgs {
 // length, then the Ethernet II type) and the datagram streams in the record-producing Tx instantiation,
 // one PktTxRecord per frame into rec — nothing is written to the ring, and a datagram flagged EXT_HDR is
 // left to the host (no walk here: REC), so the descriptors are needed in no register past the run.
-template <int D, bool NT, int BND, bool TX = false, bool REC = false>
+// SUMS (Rx; RxBurstEtherSumsHost): the tail's SUMS form, one NETCSUM_FRAG_SUM per frame into A.sums_out — a
+// frame without a datagram to check streams as {start, 0}, which parses as malformed and records 0.
+template <int D, bool NT, int BND, bool TX = false, bool REC = false, bool SUMS = false>
 __device__ __forceinline__ void pkt_ether_run(const PktBatchArgs& A, const EtherRunArgs& E, uint32_t spw, PktTxRecord* rec,
                                               uint64_t run, uint32_t w, uint32_t lane) {
     const uint64_t sb64 = run * spw;
@@ -745,7 +748,7 @@ __device__ __forceinline__ void pkt_ether_run(const PktBatchArgs& A, const Ether
     if (mine) {
         E.l2[i] = (uint8_t)h.cls;
     }
-    pkt_vl_tail<D, NT, TX, REC, 0, BND, false, false, !REC>(A, spw, rec, run, w, lane, s_begin, nres,
+    pkt_vl_tail<D, NT, TX, REC, 0, BND, false, SUMS, !REC>(A, spw, rec, run, w, lane, s_begin, nres,
                                                             h.ip ? o + NetCsum_L2HdrLen(h.cls) : o, h.ip);
 }
 
@@ -1132,16 +1135,20 @@ __device__ uint32_t burst_leader_wait(const BurstServerArgs& S, uint64_t seen, u
     }
 }
 
-template <bool TX, int BND, bool VL>
+template <bool TX, int BND, bool VL, bool SUMS = false>
 __device__ __forceinline__ void burst_serve(const PktBatchArgs& A, uint32_t spw, PktTxRecord* rec, uint32_t w,
                                             uint32_t lane) {
     const uint32_t runs = (A.n + spw - 1u) / spw;
     for (uint32_t r = blockIdx.x * 4u + w; r < runs; r += gridDim.x * 4u) {
-        pkt_stream_run<4, true, TX, TX, 0, BND, VL>(A, spw, rec, r, w, lane);
+        pkt_stream_run<4, true, TX, TX, 0, BND, VL, false, SUMS>(A, spw, rec, r, w, lane);
     }
 }
 
-__global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
+// SUMS: the instantiation that also serves Rx posts with kBurstSums (fragment payload sums). A post without
+// the bit takes the same branches in both; the `false` instantiation is never posted one with it (the host
+// stops it and launches the other, hostmem burst_server_run), and holds no SUMS code.
+template <bool SUMS>
+__global__ void __launch_bounds__(256) burst_server_kernel(std::conditional_t<SUMS, BurstServerSumsArgs, BurstServerArgs> S) {
     __shared__ uint32_t s_line[16];
     __shared__ uint32_t s_cmd;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1168,7 +1175,10 @@ __global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
             A.stride = d[4];
             A.n = d[5];
             A.len_u = d[6];
-            const uint32_t spw = d[7], form = d[8];
+            const uint32_t spw = d[7];
+            // (the kinds below compare the whole of form >> 1: the sums bit is taken out first)
+            const bool sums = SUMS && (d[8] & (kBurstSums << 1)) != 0u;
+            const uint32_t form = SUMS ? d[8] & ~(kBurstSums << 1) : d[8];
             A.udp_tx_csum = d[9];
             A.rx_cfg = d[10];
             const bool ether = ((form >> 1) & kBurstKindMask) == kBurstEther;
@@ -1200,7 +1210,25 @@ __global__ void __launch_bounds__(256) burst_server_kernel(BurstServerArgs S) {
             } else {
                 A.flags_out = S.flags;
                 A.action_out = S.act;
-                if (ether) {
+                if (sums) {
+                    if constexpr (SUMS) {
+                        // the records: plain stores beside the flags and actions, published by the same release
+                        A.sums_out = S.sums;
+                        if (ether) {
+                            const EtherRunArgs E{d[12], d[13], d[14], d[15], S.l2};
+                            const uint32_t runs = (A.n + spw - 1u) / spw;
+                            for (uint32_t r = blockIdx.x * 4u + w; r < runs; r += gridDim.x * 4u) {
+                                pkt_ether_run<4, true, 2, false, false, true>(A, E, spw, nullptr, r, w, lane);
+                            }
+                        } else if ((form >> 1) == kBurstWhole) {
+                            burst_serve<false, 0, false, true>(A, spw, nullptr, w, lane);
+                        } else if ((form >> 1) == kBurstLive) {
+                            burst_serve<false, 2, false, true>(A, spw, nullptr, w, lane);
+                        } else {
+                            burst_serve<false, 2, true, true>(A, spw, nullptr, w, lane);
+                        }
+                    }
+                } else if (ether) {
                     const EtherRunArgs E{d[12], d[13], d[14], d[15], S.l2};
                     const uint32_t runs = (A.n + spw - 1u) / spw;
                     for (uint32_t r = blockIdx.x * 4u + w; r < runs; r += gridDim.x * 4u) {
@@ -1330,11 +1358,18 @@ hipError_t launch_burst_done(const uint8_t* fl, const uint8_t* act, uint32_t n, 
     return hipGetLastError();
 }
 
-hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t s) {
+hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t s, uint32_t* sums) {
     if (blocks < 1 || blocks > kBurstServerMaxBlocks || a.post == nullptr || a.closed == nullptr) {
         return hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL(burst_server_kernel, dim3(blocks), dim3(256), 0, s, a);
+    if (sums != nullptr) {
+        BurstServerSumsArgs as{};
+        static_cast<BurstServerArgs&>(as) = a;
+        as.sums = sums;
+        hipLaunchKernelGGL(burst_server_kernel<true>, dim3(blocks), dim3(256), 0, s, as);
+    } else {
+        hipLaunchKernelGGL(burst_server_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -206,8 +206,8 @@ __device__ __forceinline__ void walk_wave(const PktBatchArgs& A, uint32_t s0, bo
 // The same for a wave that keeps its datagrams' descriptors in registers and has none in memory (the
 // burst server's Ether form): lane k holds datagram s0 + k's address `at` and octets present `avail`,
 // and a group fetches its datagram's from lane j (ds_bpermute, by all 64 lanes: a group without a
-// datagram this round reads its own lane's).
-template <bool TX>
+// datagram this round reads its own lane's). SUMS: walk_at's (the datagram's record is the group's to write).
+template <bool TX, bool SUMS = false>
 __device__ __forceinline__ void walk_wave_regs(const PktBatchArgs& A, uint32_t s0, bool need, uint32_t lane, uintptr_t at,
                                                uint32_t avail) {
     const uint32_t grp = lane / kLanes;
@@ -226,7 +226,7 @@ __device__ __forceinline__ void walk_wave_regs(const PktBatchArgs& A, uint32_t s
                             (uint32_t)__shfl((int)(uint32_t)at, src, 64);
         const uint32_t aj = (uint32_t)__shfl((int)avail, src, 64);
         if (j != ~0u) {
-            walk_at<TX>(A, s0 + j, reinterpret_cast<uint8_t*>((uintptr_t)pj), aj, lane % kLanes);
+            walk_at<TX, SUMS>(A, s0 + j, reinterpret_cast<uint8_t*>((uintptr_t)pj), aj, lane % kLanes);
         }
     }
 }

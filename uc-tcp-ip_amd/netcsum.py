@@ -263,6 +263,10 @@ def lib() -> ctypes.CDLL:
     L.NetUtil_MI355X_RxBurstEther.restype = i32
     L.NetUtil_MI355X_RxBurstEtherHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, u32, vp, vp, vp, vp, u32]
     L.NetUtil_MI355X_RxBurstEtherHost.restype = i32
+    L.NetUtil_MI355X_RxBurstEtherSums.argtypes = [vp, vp, vp, u64, u16, u32, u32, u32, vp, vp, vp, vp, vp, vp]
+    L.NetUtil_MI355X_RxBurstEtherSums.restype = i32
+    L.NetUtil_MI355X_RxBurstEtherSumsHost.argtypes = [vp, vp, vp, u64, u16, u32, u32, u32, vp, vp, vp, vp, vp, u32]
+    L.NetUtil_MI355X_RxBurstEtherSumsHost.restype = i32
     L.NetUtil_MI355X_EtherClass.argtypes = [vp, u16, u32, vp, ctypes.POINTER(ctypes.c_uint16)]
     L.NetUtil_MI355X_EtherClass.restype = ctypes.c_uint8
     L.NetUtil_MI355X_RxBurstEtherTally.argtypes = [vp, u32, vp]
@@ -691,6 +695,23 @@ def rx_burst_ether(base, n, action, l2, flags=None, off=None, lens=None, stride=
     return err
 
 
+def rx_burst_ether_sums(base, n, action, l2, sums, flags=None, off=None, lens=None, stride=0, frame_len=0, rx_cfg=0,
+                        eth_cfg=0, hw_addr=None, stream=None, check=True):
+    """NetUtil_MI355X_RxBurstEtherSums: rx_burst_ether plus one NETCSUM_FRAG_SUM {u16 sum, u16 len} per frame
+    in `sums` (4 B per frame): the payload sum and length of the fragment the frame carries, else 0."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(l2, n, "layer-2 classes")
+        _require(sums, 4 * n, "fragment sums")
+    hw = _hw_addr(hw_addr)
+    err = lib().NetUtil_MI355X_RxBurstEtherSums(_p(base), _p(off), _p(lens), stride, frame_len, n, rx_cfg, eth_cfg,
+                                                _p(hw), _p(action), _p(flags), _p(l2), _p(sums), _stream(stream))
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstEtherSums")
+    return err
+
+
 def ether_class(frame, eth_cfg=0, hw_addr=None, length=None):
     """NetUtil_MI355X_EtherClass (host logic) of one frame (bytes) -> (L2_* class, header length 14 / 22 / 0).
     length: the octets received, where they differ from len(frame)."""
@@ -838,6 +859,22 @@ def rx_burst_ether_host(base, n, action, l2, flags=None, off=None, lens=None, st
                                                 _p(action), _p(flags), _p(l2), n_chunks)
     if check:
         _check(err, "NetUtil_MI355X_RxBurstEtherHost")
+    return err
+
+
+def rx_burst_ether_sums_host(base, n, action, l2, sums, flags=None, off=None, lens=None, stride=0, frame_len=0,
+                             rx_cfg=0, eth_cfg=0, hw_addr=None, n_chunks=0, check=True):
+    """NetUtil_MI355X_RxBurstEtherSumsHost: rx_burst_ether_host plus the per-frame fragment sums (host arrays)."""
+    _frame_bounds(base, off, lens, stride, frame_len, n, flags)
+    if n:
+        _require(action, n, "actions")
+        _require(l2, n, "layer-2 classes")
+        _require(sums, 4 * n, "fragment sums")
+    hw = _hw_addr(hw_addr)
+    err = lib().NetUtil_MI355X_RxBurstEtherSumsHost(_p(base), _p(off), _p(lens), stride, frame_len, n, rx_cfg, eth_cfg,
+                                                    _p(hw), _p(action), _p(flags), _p(l2), _p(sums), n_chunks)
+    if check:
+        _check(err, "NetUtil_MI355X_RxBurstEtherSumsHost")
     return err
 
 
