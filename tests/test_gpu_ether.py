@@ -162,7 +162,8 @@ def test_rx_burst_ether_configurations(eth_cfg, hw, rx_cfg, with_flags):
 
 
 @pytest.mark.parametrize("layout,n_chunks", [("packed3", 0), ("packed3", 3), ("slot1520", 0), ("slot1520", 3),
-                                             ("slot1536", 3), ("fixed", 0), ("fixed", 3)])
+                                             ("slot1536", 3), ("fixed", 0), ("fixed", 3),
+                                             ("packed3", 7), ("slot1520", 7)])   # 7 chunks: every slot reused, the last short
 def test_rx_burst_ether_host_form(layout, n_chunks):
     b = burst(layout, 257)
     dev = run_device(b)

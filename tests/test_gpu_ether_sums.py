@@ -125,9 +125,11 @@ def run_host(b, ring, n_chunks=0, zero_copy=3, eth_cfg=MCAST, hw=ef.HW):
     return act, fl, l2, rec, launch
 
 
-@pytest.mark.parametrize("layout,n_chunks", [("packed1", 0), ("packed1", 3), ("slot1520", 0), ("slot1520", 3), ("fixed", 3)])
+@pytest.mark.parametrize("layout,n_chunks", [("packed1", 0), ("packed1", 3), ("slot1520", 0), ("slot1520", 3), ("fixed", 3),
+                                             ("packed1", 7), ("slot1520", 7)])
 def test_host_form_copy_pipeline_from_a_pageable_ring(layout, n_chunks):
-    """257 frames in 3 chunks: a chunk boundary lies inside the records."""
+    """257 frames in 3 chunks: a chunk boundary lies inside the records; in 7 chunks (6 of 37 and one of 35)
+    every pipeline slot is reused, by a form that stages offsets and lengths and by one that stages lengths."""
     b = eff.burst(layout, 257)
     dev = run_device(b)
     got = run_host(b, b.buf.copy(), n_chunks)

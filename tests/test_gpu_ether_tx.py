@@ -161,7 +161,8 @@ def test_empty_burst_under_stream_capture_is_a_no_op():
 
 
 @pytest.mark.parametrize("layout,n,n_chunks", [("packed", 1031, 0), ("packed", 1031, 3), ("slot0", 257, 1), ("slot2", 1031, 4),
-                                               ("fixed", 65, 0), ("fixed", 257, 5), ("slot0", 1, 0)])
+                                               ("fixed", 65, 0), ("fixed", 257, 5), ("slot0", 1, 0),
+                                               ("packed", 29, 7)])       # 6 chunks of 5, 5, 5, 5, 5, 4: slots reused
 def test_tx_burst_ether_host_form(layout, n, n_chunks):
     b = etx.ring(layout, n)
     for pinned in (True, False):

@@ -188,15 +188,17 @@ def test_rx_burst_sums_lane_group_kernel_and_walk_pass():
         netcsum.tune(netcsum.TUNE_KERNEL, 0)
 
 
-def test_rx_burst_sums_host_form():
+@pytest.mark.parametrize("n_chunks", [0, 3, 7])
+def test_rx_burst_sums_host_form(n_chunks):
+    """7 chunks (6 of 29 frames and one of 26): every pipeline slot is reused, and the last chunk is short."""
     n = 200
     for layout in ("packed", "pool1520"):
         buf, offs, lens, stride, lead, pkt_len, (want_f, want_a, want_s) = burst(n)[layout]
         act, fl, sums = np.full(n, 0xEE, np.uint8), np.full(n, 0xEE, np.uint8), np.full(n, 0x5A5A5A5A, np.uint32)
         if offs is not None:
-            netcsum.rx_burst_sums_host(buf, n, act, sums, flags=fl, off=offs, lens=lens)
+            netcsum.rx_burst_sums_host(buf, n, act, sums, flags=fl, off=offs, lens=lens, n_chunks=n_chunks)
         else:
-            netcsum.rx_burst_sums_host(buf[lead:], n, act, sums, flags=fl, stride=stride, pkt_len=pkt_len, n_chunks=3)
+            netcsum.rx_burst_sums_host(buf[lead:], n, act, sums, flags=fl, stride=stride, pkt_len=pkt_len, n_chunks=n_chunks)
         assert np.array_equal(fl, want_f) and np.array_equal(act, want_a)
         check_records(sums, want_s)
 

@@ -63,6 +63,21 @@ NET_ERR nchost::check_op(NETCSUM_OP op, const void* d_pseudo, CPU_INT16U pseudo_
     return NET_UTIL_ERR_NONE;
 }
 
+NET_ERR nchost::check_rx_ether(const void* base, const uint8_t* action, const uint8_t* l2, uint32_t n_frame, uint32_t rx_cfg,
+                               uint32_t eth_cfg) {
+    if (n_frame != 0 && (action == nullptr || l2 == nullptr || base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
+    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    return NET_UTIL_ERR_NONE;
+}
+
+NET_ERR nchost::check_frag_sums(const NETCSUM_FRAG_SUM* sums, uint32_t n_frame) {
+    if (n_frame != 0 && sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
+    // one record is one 4-B store (offsets of the lane-group form's buffer stores: 32 bits)
+    if (((uintptr_t)sums & 3u) != 0u || n_frame > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    return NET_UTIL_ERR_NONE;
+}
+
 namespace {
 
 // Device scratch of the packet batches (two-pass Tx records, the walk pass's flags when the caller
@@ -817,15 +832,52 @@ NET_ERR NetUtil_MI355X_RxBurstSums(const void* d_base, const uint64_t* d_off, co
                                    NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
     if (n_pkt != 0 && d_action == nullptr) return NET_ERR_FAULT_NULL_PTR;
     if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (n_pkt != 0 && d_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
-    // one record is one 4-B store (offsets of the lane-group form's buffer stores: 32 bits)
-    if (((uintptr_t)d_sums & 3u) != 0u || n_pkt > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    const NET_ERR e = check_frag_sums(d_sums, n_pkt);
+    if (e != NET_UTIL_ERR_NONE) return e;
     PktJob j = pkt_job(d_base, d_off, d_len, stride, pkt_len, n_pkt, d_flags, hip_stream);
     j.action = d_action;
     j.rx_cfg = rx_cfg;
     j.sums = d_sums;
     return pkt_batch(tls_tune, j);
 }
+
+// The demux step both Ether device forms open with, and its end. begin(): one lease of the stream's scratch
+// for the demux and the packet batch behind it — `below` bytes that pkt_batch leases in the same slot for
+// its own layouts, then the datagrams' offsets and lengths — and the demux arguments with the frames and
+// those outputs filled (the direction adds its own and launches). end(), after pkt_batch's launches: the
+// lease ends and LastLaunch gets "<name> b=<blocks> | " in front.
+struct EtherDemux {
+    ScratchLease            scratch;
+    netcsum::EtherDemuxArgs a{};
+
+    NET_ERR begin(size_t below, const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
+                  CPU_INT16U frame_len, uint32_t n_frame, uint8_t* d_l2, hipStream_t hs) {
+        int dev = 0;
+        NC_HIP(hipGetDevice(&dev));
+        const size_t n = n_frame;
+        const size_t o_off = (below + 255u) & ~(size_t)255u;
+        const size_t o_len = (o_off + 8u * n + 255u) & ~(size_t)255u;
+        NC_HIP(scratch.acquire(dev, hs, o_len + 2u * n));
+        uint8_t* sp = static_cast<uint8_t*>(scratch.ptr());
+        a.base = static_cast<const uint8_t*>(d_base);
+        a.off = d_off;
+        a.len = d_len;
+        a.stride = stride;
+        a.len_u = frame_len;
+        a.n = n_frame;
+        a.l2_out = d_l2;
+        a.off_out = reinterpret_cast<uint64_t*>(sp + o_off);
+        a.len_out = reinterpret_cast<uint16_t*>(sp + o_len);
+        return NET_UTIL_ERR_NONE;
+    }
+    NET_ERR end(const char* name) {
+        NC_HIP(scratch.end());
+        char desc[256];
+        snprintf(desc, sizeof desc, "%s b=%u | %.220s", name, netcsum::ether_demux_blocks(a.n), netcsum::last_launch());
+        netcsum::set_last_launch(desc);
+        return NET_UTIL_ERR_NONE;
+    }
+};
 
 // Rx burst of Ethernet frames: the 802.x demux pass (netcsum_ether.hip) writes each frame's class and the
 // offset/length descriptor of its IP datagram into this thread's scratch for the stream, then RxBurst's
@@ -840,52 +892,31 @@ NET_ERR NetUtil_MI355X_RxBurstSums(const void* d_base, const uint64_t* d_off, co
 // the same list, and a datagram that waits for the walk is marked in d_sums itself (kFragSumWalk), not in
 // scratch; the lane-group form's own flags (one byte per frame) are the other case, below 4 B per frame too.
 // So the descriptors lie above all of it, as they do without sums (pkt_batch's layouts: 256 + 4 n + 16 at most).
+// sums: the call is RxBurstEtherSums, whose d_sums is checked after RxBurstEther's own arguments (RxBurstSums'
+// checks); n_frame 0 succeeds without a launch.
 static NET_ERR rx_burst_ether(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
                               CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
-                              const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
+                              const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2, bool sums,
                               NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
-    if (n_frame != 0 && (d_action == nullptr || d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
-    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    NET_ERR e = check_rx_ether(d_base, d_action, d_l2, n_frame, rx_cfg, eth_cfg);
+    if (e == NET_UTIL_ERR_NONE && sums) e = check_frag_sums(d_sums, n_frame);
+    if (e != NET_UTIL_ERR_NONE) return e;
     if (n_frame == 0) return NET_UTIL_ERR_NONE;
     if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    int dev = 0;
-    NC_HIP(hipGetDevice(&dev));
     hipStream_t hs = static_cast<hipStream_t>(hip_stream);
-    const size_t n = n_frame;
-    const size_t o_off = (256u + 4u * n + 16u + 255u) & ~(size_t)255u;   // past pkt_batch's own scratch
-    const size_t o_len = (o_off + 8u * n + 255u) & ~(size_t)255u;
-    ScratchLease scratch;
-    NC_HIP(scratch.acquire(dev, hs, o_len + 2u * n));
-    uint8_t* sp = static_cast<uint8_t*>(scratch.ptr());
-    netcsum::EtherDemuxArgs a{};
-    a.base = static_cast<const uint8_t*>(d_base);
-    a.off = d_off;
-    a.len = d_len;
-    a.stride = stride;
-    a.len_u = frame_len;
-    a.n = n_frame;
-    a.eth_cfg = eth_cfg;
-    if (hw_addr != nullptr) {
-        a.have_hw = 1u;
-        a.hw_lo = (uint32_t)hw_addr[0] | ((uint32_t)hw_addr[1] << 8) | ((uint32_t)hw_addr[2] << 16) | ((uint32_t)hw_addr[3] << 24);
-        a.hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
-    }
-    a.l2_out = d_l2;
-    a.off_out = reinterpret_cast<uint64_t*>(sp + o_off);
-    a.len_out = reinterpret_cast<uint16_t*>(sp + o_len);
-    NC_HIP(netcsum::launch_ether_demux(a, hs));
-    PktJob j = pkt_job(d_base, a.off_out, a.len_out, 0, 0, n_frame, d_flags, hip_stream);
+    EtherDemux x;
+    e = x.begin(256u + 4u * (size_t)n_frame + 16u, d_base, d_off, d_len, stride, frame_len, n_frame, d_l2, hs);   // past pkt_batch's own scratch
+    if (e != NET_UTIL_ERR_NONE) return e;
+    x.a.eth_cfg = eth_cfg;
+    pack_hw_addr(hw_addr, &x.a.have_hw, &x.a.hw_lo, &x.a.hw_hi);
+    NC_HIP(netcsum::launch_ether_demux(x.a, hs));
+    PktJob j = pkt_job(d_base, x.a.off_out, x.a.len_out, 0, 0, n_frame, d_flags, hip_stream);
     j.action = d_action;
     j.rx_cfg = rx_cfg;
     j.sums = d_sums;
-    const NET_ERR e = pkt_batch(tls_tune, j);
+    e = pkt_batch(tls_tune, j);
     if (e != NET_UTIL_ERR_NONE) return e;
-    NC_HIP(scratch.end());
-    char desc[256];
-    snprintf(desc, sizeof desc, "ether_demux b=%u | %.220s", netcsum::ether_demux_blocks(n_frame), netcsum::last_launch());
-    netcsum::set_last_launch(desc);
-    return NET_UTIL_ERR_NONE;
+    return x.end("ether_demux");
 }
 
 NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
@@ -893,22 +924,15 @@ NET_ERR NetUtil_MI355X_RxBurstEther(const void* d_base, const uint64_t* d_off, c
                                     const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
                                     void* hip_stream) {
     return rx_burst_ether(d_base, d_off, d_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, d_action, d_flags, d_l2,
-                          nullptr, hip_stream);
+                          false, nullptr, hip_stream);
 }
 
-// RxBurstEther's checks in their order, then d_sums' (RxBurstSums'); n_frame 0 succeeds without a launch.
 NET_ERR NetUtil_MI355X_RxBurstEtherSums(const void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,
                                         CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
                                         const uint8_t* hw_addr, uint8_t* d_action, uint8_t* d_flags, uint8_t* d_l2,
                                         NETCSUM_FRAG_SUM* d_sums, void* hip_stream) {
-    if (n_frame != 0 && (d_action == nullptr || d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
-    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (n_frame != 0 && d_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
-    if (((uintptr_t)d_sums & 3u) != 0u || n_frame > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (n_frame == 0) return NET_UTIL_ERR_NONE;
     return rx_burst_ether(d_base, d_off, d_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, d_action, d_flags, d_l2,
-                          d_sums, hip_stream);
+                          true, d_sums, hip_stream);
 }
 
 // Tx burst of Ethernet frames: the Tx demux pass (netcsum_ether.hip ether_tx_demux_kernel) writes each
@@ -925,44 +949,26 @@ extern "C++" NET_ERR nchost::tx_burst_ether(const Tune& t, void* d_base, const u
     if (n_frame != 0 && (d_l2 == nullptr || d_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
     if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
     if (n_frame == 0) return NET_UTIL_ERR_NONE;
-    int dev = 0;
-    NC_HIP(hipGetDevice(&dev));
-    const size_t n = n_frame;
-    const size_t o_off = (256u + 8u * n + 4u * n + 16u + 255u) & ~(size_t)255u;   // past pkt_batch's own Tx scratch
-    const size_t o_len = (o_off + 8u * n + 255u) & ~(size_t)255u;
-    ScratchLease scratch;
-    NC_HIP(scratch.acquire(dev, hs, o_len + 2u * n));
-    uint8_t* sp = static_cast<uint8_t*>(scratch.ptr());
-    netcsum::EtherDemuxArgs a{};
-    a.base = static_cast<const uint8_t*>(d_base);
-    a.off = d_off;
-    a.len = d_len;
-    a.stride = stride;
-    a.len_u = frame_len;
-    a.n = n_frame;
-    a.l2_out = d_l2;
-    a.off_out = reinterpret_cast<uint64_t*>(sp + o_off);
-    a.len_out = reinterpret_cast<uint16_t*>(sp + o_len);
-    NC_HIP(netcsum::launch_ether_tx_demux(a, hs));
-    PktJob j = pkt_job(d_base, a.off_out, a.len_out, 0, 0, n_frame, d_flags, hs);
+    EtherDemux x;
+    NET_ERR e = x.begin(256u + 8u * (size_t)n_frame + 4u * (size_t)n_frame + 16u, d_base, d_off, d_len, stride, frame_len,
+                        n_frame, d_l2, hs);                  // past pkt_batch's own Tx scratch
+    if (e != NET_UTIL_ERR_NONE) return e;
+    NC_HIP(netcsum::launch_ether_tx_demux(x.a, hs));
+    PktJob j = pkt_job(d_base, x.a.off_out, x.a.len_out, 0, 0, n_frame, d_flags, hs);
     j.tx = true;
     j.udp_mode = 2u;
     j.fieldpos = d_fieldpos;
-    const NET_ERR e = pkt_batch(t, j);
+    e = pkt_batch(t, j);
     if (e != NET_UTIL_ERR_NONE) return e;
     if (d_rec != nullptr) {
         netcsum::PktBatchArgs g{};
         g.base = static_cast<const uint8_t*>(d_base);
-        g.off = a.off_out;
+        g.off = x.a.off_out;
         g.n = n_frame;
         g.fieldpos_out = d_fieldpos;
         NC_HIP(netcsum::launch_pkt_field_gather(g, d_rec, hs));
     }
-    NC_HIP(scratch.end());
-    char desc[256];
-    snprintf(desc, sizeof desc, "ether_tx_demux b=%u | %.220s", netcsum::ether_demux_blocks(n_frame), netcsum::last_launch());
-    netcsum::set_last_launch(desc);
-    return NET_UTIL_ERR_NONE;
+    return x.end("ether_tx_demux");
 }
 
 NET_ERR NetUtil_MI355X_TxBurstEther(void* d_base, const uint64_t* d_off, const uint16_t* d_len, uint64_t stride,

@@ -1,9 +1,11 @@
 // netcsum_host.h — internal declarations of the batch ABI's host layer, shared by its translation
 // units: netcsum_policy.hip (launch policy: which kernel form, geometry and run length a batch gets —
 // decisions only, no launches), netcsum_abi.hip (argument checks, tuning, scratch and plans, the
-// device-resident entry points) and netcsum_hostmem.hip (host contexts, the copy pipeline, zero-copy
-// bursts and the burst server, the host-memory entry points). The kernels' own interface is
-// netcsum_kernels.h.
+// device-resident entry points) and netcsum_hostmem.hip (host contexts, the one copy-pipeline driver and
+// the slot layout and issue step each ...Host form gives it, zero-copy bursts and the burst server, the
+// host-memory entry points). What that file decides without a device — chunk plans, slot layouts,
+// descriptor staging, the Tx record appliers — is netcsum_hostplan.h, free of HIP. The kernels' own
+// interface is netcsum_kernels.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -123,6 +125,23 @@ void pkt_settle(const Tune& t, const PktJob& j, PktPlan& p);
 PktJob pkt_job(const void* base, const uint64_t* off, const uint16_t* len, uint64_t stride, CPU_INT16U pkt_len, uint32_t n,
                uint8_t* flags, void* hip_stream);
 NET_ERR pkt_batch(const Tune& t, const PktJob& j);
+
+// ---- Ether bursts
+// The argument checks the four Rx Ether entry points share (device and host memory, with and without
+// fragment sums), each returning the first failing code in the entry points' order: check_rx_ether, then —
+// for a sums form — check_frag_sums, then n_frame 0 succeeds, then n_frame > 0x7FFFFFFF is invalid.
+NET_ERR check_rx_ether(const void* base, const uint8_t* action, const uint8_t* l2, uint32_t n_frame, uint32_t rx_cfg,
+                       uint32_t eth_cfg);
+NET_ERR check_frag_sums(const NETCSUM_FRAG_SUM* sums, uint32_t n_frame);
+
+// The interface's six address octets as the demux kernel and the burst post carry them (hw_addr nullptr:
+// promiscuous, everything left 0): octets 0-3 and 4-5, little-endian.
+inline void pack_hw_addr(const uint8_t* hw_addr, uint32_t* have_hw, uint32_t* hw_lo, uint32_t* hw_hi) {
+    if (hw_addr == nullptr) return;
+    *have_hw = 1u;
+    *hw_lo = (uint32_t)hw_addr[0] | ((uint32_t)hw_addr[1] << 8) | ((uint32_t)hw_addr[2] << 16) | ((uint32_t)hw_addr[3] << 24);
+    *hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
+}
 
 // TxBurstEther on device-visible memory (netcsum_abi.hip): the public entry point, and — with d_fieldpos
 // (zeroed by the caller) and d_rec — a chunk of the host-memory form, whose written fields come back as

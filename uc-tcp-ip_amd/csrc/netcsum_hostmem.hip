@@ -14,11 +14,13 @@
 #include <cstdio>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/netcsum_ether.h"
 #include "netcsum_device.h"
 #include "netcsum_host.h"
+#include "netcsum_hostplan.h"
 
 using namespace nchost;
 
@@ -167,8 +169,6 @@ NET_ERR ensure_pipe(HostCtx& c, size_t dev_bytes, size_t host_bytes) {
     return NET_UTIL_ERR_NONE;
 }
 
-size_t al256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
 // A host-memory batch that returns early (any error) first waits for its three pipeline streams, so
 // no copy into the caller's memory is still in flight when the call returns. (A Tx batch that fails
 // may leave the caller's buffer with some chunks finalized and others not.)
@@ -183,39 +183,86 @@ struct PipeDrainOnExit {
     }
 };
 
-// One chunk of a host-memory batch: items [s0, s0 + ns) whose bytes are [lo, hi) of the caller's buffer.
-struct HostChunk {
-    uint32_t s0, ns;
-    uint64_t lo, hi;
+static_assert(kRecFieldIP == netcsum::kFieldIP && kRecFieldL4 == netcsum::kFieldL4, "apply_field_records reads the gather's bits");
+
+// ----------------------------------------------------------- the three-slot copy pipeline
+// Every ...Host batch is its device form run over chunks (netcsum_hostplan.h plan_chunks) on the three
+// pipeline streams of the calling thread's context: chunk k's bytes [lo, hi) go H2D into slot k mod 3
+// (with its descriptors rebased to lo, staged in the slot's pinned memory), the device form runs on the
+// copy and its results come D2H, while chunks k +- 1 copy and compute on the other streams. Host buffers
+// should be pinned (hipHostMalloc / hipHostRegister) for the copies to overlap; the call returns when
+// every output is in host memory.
+struct PipeSlot {
+    hipStream_t st;
+    uint8_t*    d;      // the slot's device buffer (SlotLayout dev)
+    uint8_t*    h;      // its pinned staging (SlotLayout host)
 };
 
-// Chunks of about n / n_chunks items each; items of a strided batch (h_off == NULL) are
-// [i * stride, i * stride + len), of an offset/length batch [h_off[i], h_off[i] + h_len[i]).
-// Returns the largest chunk's byte span.
-uint64_t plan_chunks(const uint64_t* h_off, const uint16_t* h_len, uint64_t stride, uint32_t len, uint32_t n,
-                     uint32_t n_chunks, std::vector<HostChunk>& out) {
-    if (n_chunks == 0) n_chunks = 1;
-    if (n_chunks > n) n_chunks = n;
-    const uint32_t per = (n + n_chunks - 1u) / n_chunks;
-    uint64_t maxb = 0;
-    out.clear();
-    for (uint32_t s0 = 0; s0 < n; s0 += per) {
-        HostChunk k{s0, std::min(per, n - s0), 0, 0};
-        if (h_off == nullptr) {
-            k.lo = (uint64_t)s0 * stride;
-            k.hi = (uint64_t)(s0 + k.ns - 1u) * stride + len;
-        } else {
-            k.lo = ~0ull;
-            for (uint32_t i = s0; i < s0 + k.ns; ++i) {
-                k.lo = std::min<uint64_t>(k.lo, h_off[i]);
-                k.hi = std::max<uint64_t>(k.hi, h_off[i] + h_len[i]);
-            }
-            if (k.hi < k.lo) k.hi = k.lo;
+struct NoRetire { void operator()(const HostChunk&, const PipeSlot&) const {} };
+
+// Runs the chunks through the slots. issue(chunk, slot) enqueues the chunk's H2D copies, memsets, launches
+// and D2H copies on slot.st; retire(chunk, slot), where a form has one, runs on the host once that stream
+// has finished the chunk (Tx: the returned records are applied to the caller's buffer).
+// The one rule for reusing a slot: the device side of slot k mod 3 is reused in its stream's order, which
+// needs no host wait; its pinned staging is written by the host, so a form that stages anything there, or
+// retires, first waits for chunk k - 3 (synchronise, retire). At the end the last three chunks are
+// waited for and retired in order — every stream in use then is idle.
+template <class Issue, class Retire = NoRetire>
+NET_ERR run_pipe(HostCtx& c, const ChunkPlan& plan, const SlotLayout& dev, const SlotLayout& host, Issue issue,
+                 Retire retire = Retire{}) {
+    const bool host_wait = host.total() != 0u || !std::is_same<Retire, NoRetire>::value;
+    NET_ERR e = ensure_pipe(c, dev.total(), host.total());
+    if (e != NET_UTIL_ERR_NONE) return e;
+    PipeDrainOnExit guard{c};
+    const size_t n = plan.ch.size();
+    auto slot = [&](size_t k) { return PipeSlot{c.pstream[k % 3u], c.d_pipe[k % 3u], c.h_pipe[k % 3u]}; };
+    auto finish = [&](size_t k) -> NET_ERR {                 // chunk k's stream has finished: retire it
+        NC_HIP(hipStreamSynchronize(slot(k).st));
+        retire(plan.ch[k], slot(k));
+        return NET_UTIL_ERR_NONE;
+    };
+    for (size_t k = 0; k < n; ++k) {
+        if (k >= 3 && host_wait) {                           // slot k mod 3's staging is free again
+            e = finish(k - 3u);
+            if (e != NET_UTIL_ERR_NONE) return e;
         }
-        maxb = std::max<uint64_t>(maxb, k.hi - k.lo);
-        out.push_back(k);
+        e = issue(plan.ch[k], slot(k));
+        if (e != NET_UTIL_ERR_NONE) return e;
     }
-    return maxb;
+    for (size_t k = n > 3 ? n - 3 : 0; k < n; ++k) {
+        e = finish(k);
+        if (e != NET_UTIL_ERR_NONE) return e;
+    }
+    guard.done = true;
+    return NET_UTIL_ERR_NONE;
+}
+
+// A chunk's bytes [lo, hi) of the caller's buffer to the start of its slot.
+NET_ERR copy_chunk_bytes(const void* h_base, const HostChunk& q, const PipeSlot& s) {
+    if (q.hi > q.lo) {
+        NC_HIP(hipMemcpyAsync(s.d, static_cast<const uint8_t*>(h_base) + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, s.st));
+    }
+    return NET_UTIL_ERR_NONE;
+}
+
+// A chunk's descriptors, staged in the slot's pinned memory (stage_descriptors: offsets rebased to lo) and
+// copied to the slot: where present, offsets at hs_off -> o_off and lengths at hs_len -> o_len.
+NET_ERR copy_chunk_descriptors(const uint64_t* h_off, const uint16_t* h_len, const HostChunk& q, const PipeSlot& s,
+                               size_t hs_off, size_t o_off, size_t hs_len, size_t o_len) {
+    uint64_t* h_o = reinterpret_cast<uint64_t*>(s.h + hs_off);
+    uint16_t* h_l = reinterpret_cast<uint16_t*>(s.h + hs_len);
+    stage_descriptors(h_off, h_len, q, h_o, h_l);
+    if (h_off) NC_HIP(hipMemcpyAsync(s.d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, s.st));
+    if (h_len) NC_HIP(hipMemcpyAsync(s.d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, s.st));
+    return NET_UTIL_ERR_NONE;
+}
+
+// A segment batch's pseudo-headers of items [s0, s0 + ns) to o_ph of the slot.
+NET_ERR copy_chunk_pseudo(const void* h_pseudo, uint32_t pseudo_stride, uint32_t pseudo_len, const HostChunk& q,
+                          const PipeSlot& s, size_t o_ph) {
+    NC_HIP(hipMemcpyAsync(s.d + o_ph, static_cast<const uint8_t*>(h_pseudo) + (size_t)q.s0 * pseudo_stride,
+                          (size_t)(q.ns - 1u) * pseudo_stride + pseudo_len, hipMemcpyHostToDevice, s.st));
+    return NET_UTIL_ERR_NONE;
 }
 
 // Polls done() — a read of coherent pinned memory that a kernel on c.stream stores to — back to back
@@ -331,50 +378,35 @@ NET_ERR NetUtil_MI355X_ChkSumBatchStridedHost(const void* h_seg, uint64_t seg_st
     HostCtx& c = *cp;
     const size_t out_elt = (op == NETCSUM_OP_DATA_VERIFY || op == NETCSUM_OP_HDR_VERIFY) ? 1u : 2u;
     const bool has_ph = (h_pseudo != nullptr && pseudo_len != 0);
-    std::vector<HostChunk> ch;
-    const size_t seg_bytes = plan_chunks(nullptr, nullptr, seg_stride, seg_len, n_seg, n_chunks, ch);
-    const uint32_t per = ch[0].ns;
-    // Device slot per in-flight chunk: [segment bytes | pseudo bytes | outputs], 256-B aligned. Nothing is
-    // staged on the host, so slot k mod 3 is reused in its stream's order, without a host wait.
-    const size_t ph_bytes = has_ph ? (size_t)(per - 1u) * pseudo_stride + pseudo_len : 0u;
-    const size_t o_ph = al256(seg_bytes), o_out = o_ph + al256(ph_bytes);
-    e = ensure_pipe(c, o_out + al256((size_t)per * out_elt), 0u);
-    if (e != NET_UTIL_ERR_NONE) return e;
-    PipeDrainOnExit guard{c};
-    int dev = 0;
-    NC_HIP(hipGetDevice(&dev));
+    const ChunkPlan plan = plan_chunks(nullptr, nullptr, seg_stride, seg_len, n_seg, n_chunks);
+    const uint32_t per = plan.per;
+    // device slot: [segment bytes | pseudo-headers | outputs]; host slot: [] — nothing is staged on the host,
+    // so a slot is reused in its stream's order, without a host wait
+    SlotLayout dev, host;
+    dev.take(plan.max_span);
+    const size_t o_ph = dev.take(has_ph ? (size_t)(per - 1u) * pseudo_stride + pseudo_len : 0u);
+    const size_t o_out = dev.take((size_t)per * out_elt);
+    int dev_id = 0;
+    NC_HIP(hipGetDevice(&dev_id));
     const Tune& t = tune();
-    for (size_t k = 0; k < ch.size(); ++k) {
-        const HostChunk& q = ch[k];
-        hipStream_t st = c.pstream[k % 3u];
-        uint8_t* d = c.d_pipe[k % 3u];
-        NC_HIP(hipMemcpyAsync(d, static_cast<const uint8_t*>(h_seg) + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
-        if (has_ph) {
-            NC_HIP(hipMemcpyAsync(d + o_ph, static_cast<const uint8_t*>(h_pseudo) + (size_t)q.s0 * pseudo_stride,
-                                  (size_t)(q.ns - 1u) * pseudo_stride + pseudo_len, hipMemcpyHostToDevice, st));
-        }
-        const netcsum::SegBatchArgs a = seg_args(d, nullptr, nullptr, seg_stride, seg_len, has_ph ? d + o_ph : nullptr,
-                                                 pseudo_stride, has_ph ? pseudo_len : 0u, q.ns, op, d + o_out);
+    return run_pipe(c, plan, dev, host, [&](const HostChunk& q, const PipeSlot& s) -> NET_ERR {
+        NET_ERR e = copy_chunk_bytes(h_seg, q, s);
+        if (e == NET_UTIL_ERR_NONE && has_ph) e = copy_chunk_pseudo(h_pseudo, pseudo_stride, pseudo_len, q, s, o_ph);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        const netcsum::SegBatchArgs a = seg_args(s.d, nullptr, nullptr, seg_stride, seg_len, has_ph ? s.d + o_ph : nullptr,
+                                                 pseudo_stride, has_ph ? pseudo_len : 0u, q.ns, op, s.d + o_out);
         // Parity of each segment's start is derived in-kernel from the DEVICE address it reads,
         // so re-basing the chunk at a 256-B aligned device buffer is transparent.
-        NC_HIP(netcsum::launch_seg_batch(t, a, choose_cfg(t, dev, a, seg_len), st));
-        NC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(h_out) + (size_t)q.s0 * out_elt, d + o_out, (size_t)q.ns * out_elt,
-                              hipMemcpyDeviceToHost, st));
-    }
-    for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
-    guard.done = true;
-    return NET_UTIL_ERR_NONE;
+        NC_HIP(netcsum::launch_seg_batch(t, a, choose_cfg(t, dev_id, a, seg_len), s.st));
+        NC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(h_out) + (size_t)q.s0 * out_elt, s.d + o_out, (size_t)q.ns * out_elt,
+                              hipMemcpyDeviceToHost, s.st));
+        return NET_UTIL_ERR_NONE;
+    });
 }
 
 // ----------------------------------------------------------- host-memory batches (PCIe-inclusive)
 // The path starts and ends in host memory (NIC Rx buffers, IF/net_if.c:6593; socket Tx buffers,
-// Source/net_sock.c:5531). Each entry point below is its device form run over chunks on the three
-// pipeline streams of the calling thread's context: chunk k's bytes [lo, hi) go H2D (with its
-// descriptors rebased to lo, staged in pinned memory), the device form runs on the copy, its results
-// come D2H — and for Tx the chunk's bytes themselves, written back over [lo, hi) of the caller's
-// buffer — while chunks k +- 1 copy and compute on the other streams. Slot k mod 3 is reused after its
-// stream has drained it. Host buffers should be pinned (hipHostMalloc / hipHostRegister) for the
-// copies to overlap; the call returns when every output is in host memory.
+// Source/net_sock.c:5531). Each entry point below is a slot layout and an issue step for run_pipe (above).
 
 NET_ERR NetUtil_MI355X_ChkSumBatchVarLenHost(const void* h_base, const uint64_t* h_seg_off, const uint16_t* h_seg_len,
                                              const void* h_pseudo, uint32_t pseudo_stride, CPU_INT16U pseudo_len,
@@ -390,49 +422,32 @@ NET_ERR NetUtil_MI355X_ChkSumBatchVarLenHost(const void* h_base, const uint64_t*
     HostCtx& c = *cp;
     const size_t elt = (op == NETCSUM_OP_DATA_VERIFY || op == NETCSUM_OP_HDR_VERIFY) ? 1u : 2u;
     const bool has_ph = h_pseudo != nullptr && pseudo_len != 0;
-    std::vector<HostChunk> ch;
-    const uint64_t maxb = plan_chunks(h_seg_off, h_seg_len, 0, 0, n_seg, n_chunks, ch);
-    const uint32_t per = ch[0].ns;
-    const size_t ph_bytes = has_ph ? (size_t)(per - 1u) * pseudo_stride + pseudo_len : 0u;
+    const ChunkPlan plan = plan_chunks(h_seg_off, h_seg_len, 0, 0, n_seg, n_chunks);
+    const uint32_t per = plan.per;
     // device slot: [bytes | offsets | lengths | pseudo-headers | outputs]; host slot: [offsets | lengths]
-    const size_t o_off = al256(maxb), o_len = o_off + al256((size_t)per * 8u), o_ph = o_len + al256((size_t)per * 2u);
-    const size_t o_out = o_ph + al256(ph_bytes), dev_need = o_out + al256((size_t)per * elt);
-    e = ensure_pipe(c, dev_need, al256((size_t)per * 8u) + (size_t)per * 2u);
-    if (e != NET_UTIL_ERR_NONE) return e;
-    PipeDrainOnExit guard{c};
-    for (size_t k = 0; k < ch.size(); ++k) {
-        const HostChunk& q = ch[k];
-        const int j = (int)(k % 3u);
-        hipStream_t st = c.pstream[j];
-        if (k >= 3) NC_HIP(hipStreamSynchronize(st));       // slot j's staging is free again
-        uint8_t* d = c.d_pipe[j];
-        uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
-        uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + al256((size_t)per * 8u));
-        for (uint32_t i = 0; i < q.ns; ++i) {
-            h_o[i] = h_seg_off[q.s0 + i] - q.lo;
-            h_l[i] = h_seg_len[q.s0 + i];
-        }
-        NC_HIP(hipMemcpyAsync(d, static_cast<const uint8_t*>(h_base) + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
-        NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
-        NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
-        if (has_ph) {
-            NC_HIP(hipMemcpyAsync(d + o_ph, static_cast<const uint8_t*>(h_pseudo) + (size_t)q.s0 * pseudo_stride,
-                                  (size_t)(q.ns - 1u) * pseudo_stride + pseudo_len, hipMemcpyHostToDevice, st));
-        }
+    SlotLayout dev, host;
+    dev.take(plan.max_span);
+    const size_t o_off = dev.take((size_t)per * 8u), o_len = dev.take((size_t)per * 2u);
+    const size_t o_ph = dev.take(has_ph ? (size_t)(per - 1u) * pseudo_stride + pseudo_len : 0u);
+    const size_t o_out = dev.take((size_t)per * elt);
+    const size_t hs_off = host.take((size_t)per * 8u), hs_len = host.take((size_t)per * 2u);
+    return run_pipe(c, plan, dev, host, [&](const HostChunk& q, const PipeSlot& s) -> NET_ERR {
+        NET_ERR e = copy_chunk_bytes(h_base, q, s);
+        if (e == NET_UTIL_ERR_NONE) e = copy_chunk_descriptors(h_seg_off, h_seg_len, q, s, hs_off, o_off, hs_len, o_len);
+        if (e == NET_UTIL_ERR_NONE && has_ph) e = copy_chunk_pseudo(h_pseudo, pseudo_stride, pseudo_len, q, s, o_ph);
+        if (e != NET_UTIL_ERR_NONE) return e;
         // (a segment's byte parity is taken from the device address it is read at, so the copy's new
         // alignment changes nothing)
         e = launch_batch(tune(),
-                         seg_args(d, reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint16_t*>(d + o_len),
-                                  0, 0, has_ph ? d + o_ph : nullptr, pseudo_stride, has_ph ? pseudo_len : 0u, q.ns, op,
-                                  d + o_out),
-                         0u, st);
+                         seg_args(s.d, reinterpret_cast<const uint64_t*>(s.d + o_off),
+                                  reinterpret_cast<const uint16_t*>(s.d + o_len), 0, 0, has_ph ? s.d + o_ph : nullptr,
+                                  pseudo_stride, has_ph ? pseudo_len : 0u, q.ns, op, s.d + o_out),
+                         0u, s.st);
         if (e != NET_UTIL_ERR_NONE) return e;
-        NC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(h_out) + (size_t)q.s0 * elt, d + o_out, (size_t)q.ns * elt,
-                              hipMemcpyDeviceToHost, st));
-    }
-    for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
-    guard.done = true;
-    return NET_UTIL_ERR_NONE;
+        NC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(h_out) + (size_t)q.s0 * elt, s.d + o_out, (size_t)q.ns * elt,
+                              hipMemcpyDeviceToHost, s.st));
+        return NET_UTIL_ERR_NONE;
+    });
 }
 
 // ---- zero-copy bursts (NetUtil_MI355X_RxBurstHost / RxValidateIPHost up to kBurstZC frames)
@@ -696,30 +711,56 @@ static NET_ERR burst_job(HostCtx& c, const PktJob& h, PktJob* j, bool* taken) {
     return NET_UTIL_ERR_NONE;
 }
 
-// Where a burst's results arrive: one or two arrays (h[1] = 0: one) of `bytes` bytes at h[] of the
-// context's coherent host memory, set to the 0xFF sentinel no result can take; the done-kernel mode
-// writes them to d[] of the context's device memory first (the second one only with d1).
-struct BurstOut {
-    size_t h[2], d[2], bytes;
-    bool   d1;
+// What a burst waits on in the context's coherent host memory. Each result is written once, over a sentinel
+// no result can take, so no completion protocol is needed: up to three byte arrays (flags, actions, classes:
+// none of them is ever 0xFF), the 8-B Tx records (byte 7, the store mask, is 0..3) and the 4-B fragment
+// records (0xFFFFFFFF, see kBurstSums above). arm(n) sets the sentinels of n results, before the burst is
+// posted or launched; poll()(i) holds once result i has arrived in every array listed.
+extern "C++" struct BurstWait {
+    uint8_t* bytes[3] = {nullptr, nullptr, nullptr};
+    uint8_t* rec = nullptr;
+    uint8_t* sums = nullptr;
+
+    void arm(uint32_t n) const {
+        for (uint8_t* p : bytes) {
+            if (p) std::memset(p, 0xFF, n);
+        }
+        if (rec) std::memset(rec, 0xFF, (size_t)n * 8u);
+        if (sums) std::memset(sums, 0xFF, (size_t)n * 4u);
+    }
+    // The predicate of a burst that listed the first NB byte arrays, the records (REC) and the fragment
+    // records (SUMS). Which arrays it reads is fixed at compile time, as in the lambdas it replaces: the host
+    // calls it once per result and per poll, and testing at run time which arrays are listed cost an in-place
+    // Rx burst of 1024 frames 1 us of its 38 (tools/burst_latency.c, profiles/hostpipe_latency.jsonl).
+    template <int NB, bool REC, bool SUMS>
+    auto poll() const {
+        const BurstWait w = *this;
+        return [w](uint32_t i) {
+            for (int k = 0; k < NB; ++k) {
+                if (*(volatile const uint8_t*)(w.bytes[k] + i) == 0xFFu) return false;
+            }
+            if (REC && *(volatile const uint8_t*)(w.rec + 8u * i + 7u) == 0xFFu) return false;
+            return !SUMS || *(volatile const uint32_t*)(w.sums + 4u * i) != 0xFFFFFFFFu;
+        };
+    }
 };
 
 // Runs a qualified burst and returns when its results are in coherent host memory, in the mode
 // TUNE_BURST_ZERO_COPY asks for: 3 the resident server (where the burst is in its domain, else as 2),
-// 2 a launch whose results go straight into coherent memory, polled with ready(i), 1 a launch into
+// 2 a launch whose results go straight into coherent memory, polled with ready(i) (wait.poll), 1 a launch into
 // device memory and a one-wave completion kernel that copies them out and stores a tagged word.
-// point(j, r0, r1) directs the job's outputs at the arrays; `post` carries the direction's own fields.
+// point(j, r0, r1) directs the job's outputs at the arrays — Tx: the records (wait.rec) alone; Rx: flags and
+// actions (wait.bytes[0], [1]), which the done-kernel mode writes to device memory first, the actions only
+// when the caller wants them (dev_r1) —; `post` carries the direction's own fields.
 extern "C++" {
 template <class Ready, class Point>
 static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t* h_off, netcsum::BurstPost post,
-                             const BurstOut& out, Ready ready, Point point) {
-    uint8_t* h1 = out.h[1] ? c.h_burst + out.h[1] : nullptr;
-    uint8_t* h1_dev = out.h[1] ? c.h_burst_dev + out.h[1] : nullptr;
+                             const BurstWait& wait, bool dev_r1, Ready ready, Point point) {
+    auto dev_alias = [&](uint8_t* h) { return h ? c.h_burst_dev + (h - c.h_burst) : nullptr; };
+    uint8_t* h0_dev = dev_alias(wait.rec ? wait.rec : wait.bytes[0]);
+    uint8_t* h1_dev = dev_alias(wait.rec ? nullptr : wait.bytes[1]);
     const int zc = t.burst_zc;
-    if (zc >= 2) {                                      // sentinels: no flag byte or action is 0xFF, and a
-        std::memset(c.h_burst + out.h[0], 0xFF, out.bytes);   // record's store byte is 0..3
-        if (h1) std::memset(h1, 0xFF, out.bytes);
-    }
+    if (zc >= 2) wait.arm(j.n);
     uint32_t form = 0, spw = 0;
     if (zc == 3 && server_form(h_off, j.stride, j.pkt_len, j.n, &form, &spw)) {   // the resident server
         post.ring = reinterpret_cast<uint64_t>(j.base);
@@ -727,13 +768,13 @@ static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t
         post.n = j.n;
         post.pkt_len = j.pkt_len;
         post.spw = spw;
-        if (!j.tx && j.sums != nullptr) form |= netcsum::kBurstSums;   // (the records: the caller's sentinel and wait)
+        if (!j.tx && j.sums != nullptr) form |= netcsum::kBurstSums;   // (the records: wait.sums)
         post.form = (form << 1) | (j.tx ? 1u : 0u);
         server_launch_name(form, spw, j.tx);
         return burst_server_run(t, c, post, ready, j.n);
     }
     if (zc >= 2) {                                      // results straight into coherent memory, polled
-        point(j, c.h_burst_dev + out.h[0], h1_dev);
+        point(j, h0_dev, h1_dev);
         const NET_ERR e = pkt_batch(t, j);
         if (e != NET_UTIL_ERR_NONE) return e;
         mark_zero_copy_launch(2);
@@ -743,8 +784,8 @@ static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t
             return i == j.n;
         });
     }
-    uint8_t* d0 = c.d_burst + out.d[0];
-    uint8_t* d1 = out.d1 ? c.d_burst + out.d[1] : nullptr;
+    uint8_t* d0 = c.d_burst + (wait.rec ? kBurstDevRec : 0u);   // (device side: [flags | actions | Tx records])
+    uint8_t* d1 = dev_r1 ? c.d_burst + kBurstZC : nullptr;
     point(j, d0, d1);
     const NET_ERR e = pkt_batch(t, j);
     if (e != NET_UTIL_ERR_NONE) return e;
@@ -752,7 +793,7 @@ static NET_ERR burst_deliver(const Tune& t, HostCtx& c, PktJob j, const uint64_t
     if (++c.seq == 0u) c.seq = 1u;
     const uint32_t tag = c.seq;
     *reinterpret_cast<volatile unsigned long long*>(c.h_burst + kBurstWord) = 0ull;
-    NC_HIP(netcsum::launch_burst_done(d0, d1, (uint32_t)out.bytes, c.h_burst_dev + out.h[0], h1_dev,
+    NC_HIP(netcsum::launch_burst_done(d0, d1, wait.rec ? 8u * j.n : j.n, h0_dev, h1_dev,
                                       reinterpret_cast<unsigned long long*>(c.h_burst_dev + kBurstWord), tag, c.stream));
     volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(c.h_burst + kBurstWord);
     return spin_until(c, "burst completion word", [&] { return (uint32_t)*w == tag; });
@@ -778,54 +819,140 @@ static NET_ERR rx_burst_zero_copy(const Tune& t, HostCtx& c, const PktJob& h, bo
     if (e != NET_UTIL_ERR_NONE || !*taken) return e;
     netcsum::BurstPost post{};
     post.rx_cfg = h.rx_cfg;
-    const uint8_t* hf = c.h_burst + kBurstFlags;
-    const uint8_t* ha = c.h_burst + kBurstAct;
-    const uint8_t* hs = c.h_burst + kBurstSums;
-    const BurstOut out{{kBurstFlags, kBurstAct}, {0u, kBurstZC}, h.n, h.action != nullptr};
+    BurstWait wait;
+    wait.bytes[0] = c.h_burst + kBurstFlags;
+    wait.bytes[1] = c.h_burst + kBurstAct;
+    if (h_sums) wait.sums = c.h_burst + kBurstSums;
     auto point = [](PktJob& q, uint8_t* r0, uint8_t* r1) { q.flags = r0; q.action = r1; };
-    if (h_sums != nullptr) {
-        std::memset(c.h_burst + kBurstSums, 0xFF, (size_t)h.n * 4u);
-        e = burst_deliver(t, c, j, h.off, post, out,
-                          [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                                   *(volatile const uint8_t*)(ha + i) != 0xFFu &&
-                                                   *(volatile const uint32_t*)(hs + 4u * i) != 0xFFFFFFFFu; },
-                          point);
-    } else {
-        e = burst_deliver(t, c, j, h.off, post, out,
-                          [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                                   *(volatile const uint8_t*)(ha + i) != 0xFFu; },
-                          point);
-    }
+    // (the predicate's set of arrays is a compile-time choice, see BurstWait::poll: one call per set)
+    e = h_sums ? burst_deliver(t, c, j, h.off, post, wait, h.action != nullptr, wait.poll<2, false, true>(), point)
+               : burst_deliver(t, c, j, h.off, post, wait, h.action != nullptr, wait.poll<2, false, false>(), point);
     if (e != NET_UTIL_ERR_NONE) return e;
-    if (h.flags) std::memcpy(h.flags, hf, h.n);
-    if (h.action) std::memcpy(h.action, ha, h.n);
-    if (h_sums) std::memcpy(h_sums, hs, (size_t)h.n * 4u);
+    if (h.flags) std::memcpy(h.flags, wait.bytes[0], h.n);
+    if (h.action) std::memcpy(h.action, wait.bytes[1], h.n);
+    if (h_sums) std::memcpy(h_sums, wait.sums, (size_t)h.n * 4u);
     return NET_UTIL_ERR_NONE;
 }
 
-static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks);
+// Packet batches from host memory: RxValidateIP / TxFinalizeIP / RxBurst / TxBurst over the chunks.
+// Tx: the device form runs on the chunk's copy and records which checksum fields it wrote
+// (fieldpos); a gather pass packs them into 8-B records, only those return D2H, and the host writes
+// the fields into its own buffer once the chunk's stream has drained (run_pipe's retire step) — 8 B per
+// datagram over PCIe instead of the chunk's bytes.
+static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks) {
+    const uint64_t* h_off = h.off;
+    const uint16_t* h_len = h.len;
+    const uint64_t stride = h.stride;
+    const uint32_t n_pkt = h.n;
+    uint8_t* h_flags = h.flags;
+    uint8_t* h_action = h.action;
+    NETCSUM_FRAG_SUM* h_sums = h.sums;                       // (RxBurstSumsHost: 4 B more per frame D2H)
+    const bool tx = h.tx;
+    HostCtx* cp = nullptr;
+    NET_ERR e = host_ctx(&cp);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    // n_chunks 0 = the library's choice (tools/burst_latency.c, profiles/r3x_burst_latency.jsonl): each
+    // chunk adds 15-20 us per call and PCIe stays the bound, so one chunk, except Tx from 32 Ki
+    // datagrams, whose host-side field write-back overlaps the later chunks' copies (262 144 frames:
+    // 16 chunks 7.4 ms, one 8.4 ms)
+    if (n_chunks == 0) n_chunks = tx ? std::min(16u, std::max(1u, n_pkt / 16384u)) : 1u;
+    if (n_pkt / n_chunks > (1u << 28)) n_chunks = (n_pkt >> 28) + 1u;   // records: 32-bit offsets
+    const ChunkPlan plan = plan_chunks(h_off, h_len, stride, h.pkt_len, n_pkt, n_chunks);
+    const bool varlen = h_off != nullptr;
+    const size_t per = plan.per;
+    // device slot: [bytes | offsets | lengths | flags | actions | field positions | records | fragment sums];
+    // host slot: [offsets | lengths | records]
+    SlotLayout dev, host;
+    dev.take(plan.max_span);
+    const size_t o_off = dev.take(varlen ? per * 8u : 0u), o_len = dev.take(varlen ? per * 2u : 0u);
+    const size_t o_fl = dev.take(per), o_act = dev.take(per);
+    const size_t o_fp = dev.take(tx ? per * 4u : 0u), o_rec = dev.take(tx ? per * 8u : 0u);
+    const size_t o_sum = dev.take(h_sums ? per * sizeof(NETCSUM_FRAG_SUM) : 0u);
+    const size_t hs_off = host.take(varlen ? per * 8u : 0u), hs_len = host.take(varlen ? per * 2u : 0u);
+    const size_t hs_rec = host.take(tx ? per * 8u : 0u);
+    uint8_t* hb = static_cast<uint8_t*>(const_cast<void*>(h.base));
+    auto issue = [&](const HostChunk& q, const PipeSlot& s) -> NET_ERR {
+        uint8_t* d = s.d;
+        NET_ERR e = copy_chunk_bytes(hb, q, s);
+        if (e == NET_UTIL_ERR_NONE) e = copy_chunk_descriptors(h_off, h_len, q, s, hs_off, o_off, hs_len, o_len);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        uint32_t* d_fp = tx ? reinterpret_cast<uint32_t*>(d + o_fp) : nullptr;
+        if (tx) NC_HIP(hipMemsetAsync(d_fp, 0, (size_t)q.ns * 4u, s.st));   // a packet no kernel wrote: no fields
+        const uint64_t* d_o = varlen ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr;
+        PktJob job = h;                                      // the chunk's copy on the device
+        job.base = d;
+        job.off = d_o;
+        job.len = varlen ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr;
+        job.n = q.ns;
+        job.flags = h_flags ? d + o_fl : nullptr;
+        job.action = h_action ? d + o_act : nullptr;
+        job.fieldpos = d_fp;
+        job.sums = h_sums ? reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum) : nullptr;
+        job.stream = s.st;
+        e = pkt_batch(t, job);
+        if (e != NET_UTIL_ERR_NONE) return e;
+        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, s.st));
+        if (h_action) NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, s.st));
+        if (h_sums) {
+            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, s.st));
+        }
+        if (tx) {
+            netcsum::PktBatchArgs g{};
+            g.base = d;
+            g.off = d_o;
+            g.stride = stride;
+            g.n = q.ns;
+            g.fieldpos_out = d_fp;
+            uint64_t* d_rec = reinterpret_cast<uint64_t*>(d + o_rec);
+            NC_HIP(netcsum::launch_pkt_field_gather(g, d_rec, s.st));
+            NC_HIP(hipMemcpyAsync(s.h + hs_rec, d_rec, (size_t)q.ns * 8u, hipMemcpyDeviceToHost, s.st));
+        }
+        return NET_UTIL_ERR_NONE;
+    };
+    if (!tx) return run_pipe(*cp, plan, dev, host, issue);   // (fixed-length Rx stages nothing: no host wait)
+    return run_pipe(*cp, plan, dev, host, issue, [&](const HostChunk& q, const PipeSlot& s) {
+        apply_field_records(hb, h_off, stride, q.s0, q.ns, reinterpret_cast<const uint64_t*>(s.h + hs_rec));
+    });
+}
+
+// The datagrams an in-place Tx burst left alone (apply_tx_records: flag EXT_HDR, the rare IPv6 chains that
+// run past the kernel's window and are walked by a later pass in the device forms), finished by the copy
+// path as an offset/length batch of just those under the burst's UDP policy; their flags go to their
+// places, and LastLaunch names both paths.
+static NET_ERR tx_finish_skipped(const Tune& t, const void* h_base, const TxSkipped& skip, uint32_t udp_mode,
+                                 uint8_t* h_flags) {
+    if (skip.idx.empty()) return NET_UTIL_ERR_NONE;
+    const uint32_t m = (uint32_t)skip.idx.size();
+    std::vector<uint8_t> fl(m);
+    char zc_name[256];
+    snprintf(zc_name, sizeof zc_name, "%s", NetUtil_MI355X_LastLaunch());
+    PktJob rest = pkt_job(h_base, skip.off.data(), skip.len.data(), 0, 0, m, h_flags ? fl.data() : nullptr, nullptr);
+    rest.tx = true;
+    rest.udp_mode = udp_mode;
+    const NET_ERR e = pkt_host_copy(t, rest, 1u);
+    if (e != NET_UTIL_ERR_NONE) return e;
+    char d[256];
+    snprintf(d, sizeof d, "%.180s +copy path for %u EXT_HDR datagrams", zc_name, m);
+    netcsum::set_last_launch(d);
+    if (h_flags) {
+        for (uint32_t k = 0; k < m; ++k) h_flags[skip.idx[k]] = fl[k];
+    }
+    return NET_UTIL_ERR_NONE;
+}
 
 // Tx over a pinned ring: the checksum pass reads the ring in place and writes one 8-B
 // record per datagram (PktTxRecord) to device memory — never into the ring —, the completion kernel
-// copies the records into coherent pinned memory, and the host writes the fields into its ring (as
-// the copy pipeline's gather records do). Datagrams whose IPv6 extension chain runs past the
-// kernel's window (flag EXT_HDR: walked by a later pass in the device forms) are finished by the copy
-// path afterwards, as an offset/length batch of just those datagrams. *taken as for Rx.
+// copies the records into coherent pinned memory, and the host writes the fields into its ring
+// (apply_tx_records; datagrams flagged EXT_HDR: tx_finish_skipped). *taken as for Rx.
 static NET_ERR tx_burst_zero_copy(const Tune& t, HostCtx& c, const PktJob& h, bool* taken) {
-    const uint64_t* h_off = h.off;                      // (locals: the record loop below stores through
-    const uint16_t* h_len = h.len;                      // byte pointers, which may alias h)
-    const uint64_t stride = h.stride;
-    const CPU_INT16U pkt_len = h.pkt_len;
-    const uint32_t n_pkt = h.n;
-    uint8_t* h_flags = h.flags;
     *taken = false;
-    if (n_pkt > kBurstZC || t.kernel == 2) return NET_UTIL_ERR_NONE;
+    if (h.n > kBurstZC || t.kernel == 2) return NET_UTIL_ERR_NONE;
     netcsum::PktBatchArgs a{};
-    a.stride = stride;
-    a.len_u = pkt_len;
-    a.n = n_pkt;
-    a.off = h_off;                                      // (only tested against nullptr here)
-    a.len = h_len;
+    a.stride = h.stride;
+    a.len_u = h.pkt_len;
+    a.n = h.n;
+    a.off = h.off;                                      // (only tested against nullptr here)
+    a.len = h.len;
     // the records come from the run-stream kernel only: the burst qualifies where pkt_batch picks it
     // (the tuned bound, else the whole-span form 0 or the live-piece form 2), and the server's form
     // where the server serves it (server_form: strided dense, sparse and offset/length rings)
@@ -839,172 +966,13 @@ static NET_ERR tx_burst_zero_copy(const Tune& t, HostCtx& c, const PktJob& h, bo
     if (e != NET_UTIL_ERR_NONE || !*taken) return e;
     netcsum::BurstPost post{};
     post.udp_mode = h.udp_mode;
-    const uint8_t* hr = c.h_burst + kBurstRec;
-    e = burst_deliver(t, c, j, h_off, post, BurstOut{{kBurstRec, 0u}, {kBurstDevRec, 0u}, (size_t)n_pkt * 8u, false},
-                      [&](uint32_t i) { return *(volatile const uint8_t*)(hr + 8u * i + 7u) != 0xFFu; },
-                      [](PktJob& q, uint8_t* r0, uint8_t*) { q.rec_only = reinterpret_cast<netcsum::PktTxRecord*>(r0); });
+    BurstWait wait;
+    wait.rec = c.h_burst + kBurstRec;
+    e = burst_deliver(t, c, j, h.off, post, wait, false, wait.poll<0, true, false>(), [](PktJob& q, uint8_t* r0, uint8_t*) { q.rec_only = reinterpret_cast<netcsum::PktTxRecord*>(r0); });
     if (e != NET_UTIL_ERR_NONE) return e;
-    uint8_t* hb = static_cast<uint8_t*>(const_cast<void*>(h.base));
-    const uint64_t* rec = reinterpret_cast<const uint64_t*>(c.h_burst + kBurstRec);
-    std::vector<uint64_t> walk_off;
-    std::vector<uint16_t> walk_len;
-    std::vector<uint32_t> walk_idx;
-    for (uint32_t i = 0; i < n_pkt; ++i) {
-        const uint64_t r = rec[i];                      // PktTxRecord: vals | l4_off << 32 | flags << 48 | store << 56
-        const uint32_t flags = (uint32_t)(r >> 48) & 0xFFu, store = (uint32_t)(r >> 56);
-        const uint64_t o = h_off ? h_off[i] : (uint64_t)i * stride;
-        if (flags & NETCSUM_PKT_EXT_HDR) {
-            walk_off.push_back(o);
-            walk_len.push_back(h_off ? h_len[i] : pkt_len);
-            walk_idx.push_back(i);
-            continue;
-        }
-        uint8_t* p = hb + o;
-        const uint16_t ip = (uint16_t)r, l4 = (uint16_t)(r >> 16);
-        if (store & 1u) std::memcpy(p + 10, &ip, 2);
-        if (store & 2u) std::memcpy(p + ((r >> 32) & 0xFFFFu), &l4, 2);
-        if (h_flags) h_flags[i] = (uint8_t)flags;
-    }
-    if (!walk_off.empty()) {                            // the rare long IPv6 chains: the copy path
-        const uint32_t m = (uint32_t)walk_off.size();
-        std::vector<uint8_t> fl(m);
-        char zc_name[256];
-        snprintf(zc_name, sizeof zc_name, "%s", NetUtil_MI355X_LastLaunch());
-        PktJob rest = pkt_job(h.base, walk_off.data(), walk_len.data(), 0, 0, m, h_flags ? fl.data() : nullptr, nullptr);
-        rest.tx = true;
-        rest.udp_mode = h.udp_mode;
-        e = pkt_host_copy(t, rest, 1u);
-        if (e != NET_UTIL_ERR_NONE) return e;
-        char d[256];
-        snprintf(d, sizeof d, "%.180s +copy path for %u EXT_HDR datagrams", zc_name, m);
-        netcsum::set_last_launch(d);
-        if (h_flags) {
-            for (uint32_t k = 0; k < m; ++k) h_flags[walk_idx[k]] = fl[k];
-        }
-    }
-    return NET_UTIL_ERR_NONE;
-}
-
-// Tx records returned from the device for a chunk of a host-memory Tx batch: the checksum fields
-// written into the caller's host buffer (memcpy of the bytes as the device wrote them).
-static void apply_field_records(uint8_t* h_base, const uint64_t* h_off, uint64_t stride, uint32_t s0, uint32_t ns,
-                                const uint64_t* rec) {
-    for (uint32_t i = 0; i < ns; ++i) {
-        const uint64_t r = rec[i];
-        const uint32_t pos = (uint32_t)(r >> 32);
-        if ((pos & (netcsum::kFieldIP | netcsum::kFieldL4)) == 0u) continue;
-        uint8_t* p = h_base + (h_off ? h_off[s0 + i] : (uint64_t)(s0 + i) * stride);
-        const uint16_t ip = (uint16_t)r, l4 = (uint16_t)(r >> 16);
-        if (pos & netcsum::kFieldIP) std::memcpy(p + 10, &ip, 2);
-        if (pos & netcsum::kFieldL4) std::memcpy(p + (pos & 0xFFFFu), &l4, 2);
-    }
-}
-
-// Packet batches from host memory: RxValidateIP / TxFinalizeIP / RxBurst / TxBurst over the chunks.
-// Tx: the device form runs on the chunk's copy and records which checksum fields it wrote
-// (fieldpos); a gather pass packs them into 8-B records, only those return D2H, and the host writes
-// the fields into its own buffer once the chunk's stream has drained (before its slot is reused,
-// and at the end) — 8 B per datagram over PCIe instead of the chunk's bytes.
-static NET_ERR pkt_host_copy(const Tune& t, const PktJob& h, uint32_t n_chunks) {
-    const uint64_t* h_off = h.off;
-    const uint16_t* h_len = h.len;
-    const uint64_t stride = h.stride;
-    const uint32_t n_pkt = h.n;
-    uint8_t* h_flags = h.flags;
-    uint8_t* h_action = h.action;
-    NETCSUM_FRAG_SUM* h_sums = h.sums;                       // (RxBurstSumsHost: 4 B more per frame D2H)
-    const bool tx = h.tx;
-    HostCtx* cp = nullptr;
-    NET_ERR e = host_ctx(&cp);
-    if (e != NET_UTIL_ERR_NONE) return e;
-    HostCtx& c = *cp;
-    std::vector<HostChunk> ch;
-    // n_chunks 0 = the library's choice (tools/burst_latency.c, profiles/r3x_burst_latency.jsonl): each
-    // chunk adds 15-20 us per call and PCIe stays the bound, so one chunk, except Tx from 32 Ki
-    // datagrams, whose host-side field write-back overlaps the later chunks' copies (262 144 frames:
-    // 16 chunks 7.4 ms, one 8.4 ms)
-    if (n_chunks == 0) n_chunks = tx ? std::min(16u, std::max(1u, n_pkt / 16384u)) : 1u;
-    if (n_pkt / n_chunks > (1u << 28)) n_chunks = (n_pkt >> 28) + 1u;   // records: 32-bit offsets
-    const uint64_t maxb = plan_chunks(h_off, h_len, stride, h.pkt_len, n_pkt, n_chunks, ch);
-    const bool varlen = h_off != nullptr;
-    const uint32_t per = ch[0].ns;
-    // device slot: [bytes | offsets | lengths | flags | actions | field positions | records | fragment sums];
-    // host slot: [offsets | lengths | records]
-    const size_t o_off = al256(maxb), o_len = o_off + al256(varlen ? (size_t)per * 8u : 0u);
-    const size_t o_fl = o_len + al256(varlen ? (size_t)per * 2u : 0u), o_act = o_fl + al256(per);
-    const size_t o_fp = o_act + al256(per), o_rec = o_fp + al256(tx ? (size_t)per * 4u : 0u);
-    const size_t h_rec = varlen ? al256((size_t)per * 8u) + al256((size_t)per * 2u) : 0u;
-    const size_t o_sum = o_rec + al256(tx ? (size_t)per * 8u : 0u);
-    e = ensure_pipe(c, o_sum + al256(h_sums ? (size_t)per * sizeof(NETCSUM_FRAG_SUM) : 0u), h_rec + (tx ? (size_t)per * 8u : 0u));
-    if (e != NET_UTIL_ERR_NONE) return e;
-    PipeDrainOnExit guard{c};
-    uint8_t* hb = static_cast<uint8_t*>(const_cast<void*>(h.base));
-    auto drain = [&](size_t k) -> NET_ERR {                  // chunk k's stream has finished: apply its records
-        NC_HIP(hipStreamSynchronize(c.pstream[k % 3u]));
-        if (tx) {
-            apply_field_records(hb, h_off, stride, ch[k].s0, ch[k].ns,
-                                reinterpret_cast<const uint64_t*>(c.h_pipe[k % 3u] + h_rec));
-        }
-        return NET_UTIL_ERR_NONE;
-    };
-    for (size_t k = 0; k < ch.size(); ++k) {
-        const HostChunk& q = ch[k];
-        const int j = (int)(k % 3u);
-        hipStream_t st = c.pstream[j];
-        uint8_t* d = c.d_pipe[j];
-        if (k >= 3 && (varlen || tx)) {                      // slot j's staging is free again
-            e = drain(k - 3u);
-            if (e != NET_UTIL_ERR_NONE) return e;
-        }
-        NC_HIP(hipMemcpyAsync(d, hb + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
-        if (varlen) {
-            uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
-            uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + al256((size_t)per * 8u));
-            for (uint32_t i = 0; i < q.ns; ++i) {
-                h_o[i] = h_off[q.s0 + i] - q.lo;
-                h_l[i] = h_len[q.s0 + i];
-            }
-            NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
-            NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
-        }
-        uint32_t* d_fp = tx ? reinterpret_cast<uint32_t*>(d + o_fp) : nullptr;
-        if (tx) NC_HIP(hipMemsetAsync(d_fp, 0, (size_t)q.ns * 4u, st));   // a packet no kernel wrote: no fields
-        const uint64_t* d_o = varlen ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr;
-        PktJob job = h;                                      // the chunk's copy on the device
-        job.base = d;
-        job.off = d_o;
-        job.len = varlen ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr;
-        job.n = q.ns;
-        job.flags = h_flags ? d + o_fl : nullptr;
-        job.action = h_action ? d + o_act : nullptr;
-        job.fieldpos = d_fp;
-        job.sums = h_sums ? reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum) : nullptr;
-        job.stream = st;
-        e = pkt_batch(t, job);
-        if (e != NET_UTIL_ERR_NONE) return e;
-        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
-        if (h_action) NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, st));
-        if (h_sums) {
-            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, st));
-        }
-        if (tx) {
-            netcsum::PktBatchArgs g{};
-            g.base = d;
-            g.off = d_o;
-            g.stride = stride;
-            g.n = q.ns;
-            g.fieldpos_out = d_fp;
-            uint64_t* d_rec = reinterpret_cast<uint64_t*>(d + o_rec);
-            NC_HIP(netcsum::launch_pkt_field_gather(g, d_rec, st));
-            NC_HIP(hipMemcpyAsync(c.h_pipe[j] + h_rec, d_rec, (size_t)q.ns * 8u, hipMemcpyDeviceToHost, st));
-        }
-    }
-    for (size_t k = ch.size() > 3 ? ch.size() - 3 : 0; k < ch.size(); ++k) {
-        e = drain(k);
-        if (e != NET_UTIL_ERR_NONE) return e;
-    }
-    guard.done = true;
-    return NET_UTIL_ERR_NONE;
+    const TxSkipped skip = apply_tx_records(reinterpret_cast<const uint64_t*>(wait.rec), static_cast<uint8_t*>(const_cast<void*>(h.base)),
+                                            h.off, h.len, h.stride, h.pkt_len, 0u, h.n, h.flags);
+    return tx_finish_skipped(t, h.base, skip, h.udp_mode, h.flags);
 }
 
 // h: the batch with HOST pointers.
@@ -1066,183 +1034,144 @@ NET_ERR NetUtil_MI355X_RxBurstSumsHost(const void* h_base, const uint64_t* h_off
     return pkt_host(h, n_chunks);
 }
 
-// The octets [lo, hi) from the base that frames s0 .. s0 + ns - 1 of an Ether burst occupy (offsets and
-// received lengths come separately there: a ring of slots has lengths and no offsets).
-static void ether_span(const uint64_t* h_off, const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t s0,
-                       uint32_t ns, uint64_t* lo, uint64_t* hi) {
-    *lo = ~0ull;
-    *hi = 0;
-    for (uint32_t i = s0; i < s0 + ns; ++i) {
-        const uint64_t o = h_off ? h_off[i] : (uint64_t)i * stride;
-        *lo = std::min<uint64_t>(*lo, o);
-        *hi = std::max<uint64_t>(*hi, o + (h_len ? h_len[i] : frame_len));
-    }
-}
+// ---- Ether bursts (RxBurstEtherHost, TxBurstEtherHost and the sums form)
+// The front of an Ether burst over a pinned ring in place, by the resident server's Ether forms
+// (netcsum_pktstream.hip pkt_ether_run: the wave that owns a run classifies its frames and streams their
+// datagrams). Taken under rx_burst_zero_copy's conditions — at most kBurstZC frames whose span is one pinned
+// allocation of at most kBurstZCSpan bytes —; the callers ask in the server's mode only
+// (TUNE_BURST_ZERO_COPY 3: the launch-per-burst experiments are not extended to frames). *taken = false: the
+// caller takes the copy pipeline. Else the descriptors the burst gives are staged in the context's coherent
+// memory, and b holds the form (with kBurstEtherOff / kBurstEtherLen), the run length and a post with the
+// ring and its geometry filled; the direction adds its own fields and the form's direction and sums bits.
+struct EtherBurst {
+    uint32_t           form = netcsum::kBurstEther;
+    uint32_t           spw = 0;
+    netcsum::BurstPost post{};                              // (every field a form does not use: 0)
+};
 
-// An Ether burst over a pinned ring in place, by the resident server's Ether form (netcsum_pktstream.hip
-// pkt_ether_run: the wave that owns a run classifies its frames and streams their datagrams): the
-// descriptors the burst gives are staged in the context's coherent memory, flags, actions and classes
-// arrive there behind 0xFF sentinels (no class is >= 16), and the host polls all three. Taken under
-// rx_burst_zero_copy's conditions — at most kBurstZC frames whose span is one pinned allocation of at
-// most kBurstZCSpan bytes — and in the server's mode only (TUNE_BURST_ZERO_COPY 3: the launch-per-burst
-// experiments are not extended to frames). *taken = false: the caller takes the copy pipeline.
-// h_sums (RxBurstEtherSumsHost): the post carries kBurstSums, and the frames' records arrive behind their own
-// sentinel (0xFFFFFFFF, kBurstSums) and are polled with the rest.
-static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h_base, const uint64_t* h_off,
-                                        const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t n,
-                                        uint32_t rx_cfg, uint32_t eth_cfg, const uint8_t* hw_addr, uint8_t* h_action,
-                                        uint8_t* h_flags, uint8_t* h_l2, NETCSUM_FRAG_SUM* h_sums, bool* taken) {
+static NET_ERR ether_burst_setup(HostCtx& c, const void* h_base, const uint64_t* h_off, const uint16_t* h_len,
+                                 uint64_t stride, CPU_INT16U frame_len, uint32_t n, EtherBurst* b, bool* taken) {
     *taken = false;
     if (n > kBurstZC) return NET_UTIL_ERR_NONE;
-    uint64_t lo = 0, hi = 0;
-    ether_span(h_off, h_len, stride, frame_len, 0u, n, &lo, &hi);
-    if (hi <= lo || hi - lo > kBurstZCSpan) return NET_UTIL_ERR_NONE;
-    const uint8_t* d_lo = pinned_alias(static_cast<const uint8_t*>(h_base) + lo, hi - lo);
+    const HostChunk all = chunk_span(h_off, h_len, stride, frame_len, 0u, n);
+    if (all.hi <= all.lo || all.hi - all.lo > kBurstZCSpan) return NET_UTIL_ERR_NONE;
+    const uint8_t* d_lo = pinned_alias(static_cast<const uint8_t*>(h_base) + all.lo, all.hi - all.lo);
     if (d_lo == nullptr) return NET_UTIL_ERR_NONE;
     *taken = true;
     NET_ERR e = ensure_burst(c);
     if (e != NET_UTIL_ERR_NONE) return e;
-    uint32_t form = netcsum::kBurstEther;
-    const uint32_t spw = server_run(n);                     // (as the offset/length form)
+    b->spw = server_run(n);                                 // (as the offset/length form)
     if (h_off) {
         std::memcpy(c.h_burst + kBurstOff, h_off, (size_t)n * 8u);
-        form |= netcsum::kBurstEtherOff;
+        b->form |= netcsum::kBurstEtherOff;
     }
     if (h_len) {
         std::memcpy(c.h_burst + kBurstLen, h_len, (size_t)n * 2u);
-        form |= netcsum::kBurstEtherLen;
+        b->form |= netcsum::kBurstEtherLen;
     }
-    uint8_t* hf = c.h_burst + kBurstFlags;
-    uint8_t* ha = c.h_burst + kBurstAct;
-    uint8_t* hl = c.h_burst + kBurstL2;
-    uint8_t* hs = c.h_burst + kBurstSums;
-    std::memset(hf, 0xFF, n);
-    std::memset(ha, 0xFF, n);
-    std::memset(hl, 0xFF, n);
+    b->post.ring = reinterpret_cast<uint64_t>(d_lo - all.lo);   // the base's alias: offsets count from it
+    b->post.stride = (uint32_t)stride;
+    b->post.n = n;
+    b->post.pkt_len = frame_len;
+    b->post.spw = b->spw;
+    return NET_UTIL_ERR_NONE;
+}
+
+// Rx: flags, actions and classes arrive in coherent memory behind 0xFF sentinels (no class is >= 16), and the
+// host polls all three. h_sums (RxBurstEtherSumsHost): the post carries kBurstSums, and the frames' records
+// arrive behind their own sentinel (0xFFFFFFFF, kBurstSums) and are polled with the rest.
+static NET_ERR rx_burst_ether_zero_copy(const Tune& t, HostCtx& c, const void* h_base, const uint64_t* h_off,
+                                        const uint16_t* h_len, uint64_t stride, CPU_INT16U frame_len, uint32_t n,
+                                        uint32_t rx_cfg, uint32_t eth_cfg, const uint8_t* hw_addr, uint8_t* h_action,
+                                        uint8_t* h_flags, uint8_t* h_l2, NETCSUM_FRAG_SUM* h_sums, bool* taken) {
+    EtherBurst b;
+    NET_ERR e = ether_burst_setup(c, h_base, h_off, h_len, stride, frame_len, n, &b, taken);
+    if (e != NET_UTIL_ERR_NONE || !*taken) return e;
+    BurstWait wait;
+    wait.bytes[0] = c.h_burst + kBurstFlags;
+    wait.bytes[1] = c.h_burst + kBurstAct;
+    wait.bytes[2] = c.h_burst + kBurstL2;
     if (h_sums) {
-        std::memset(hs, 0xFF, (size_t)n * 4u);
-        form |= netcsum::kBurstSums;
+        wait.sums = c.h_burst + kBurstSums;
+        b.form |= netcsum::kBurstSums;
     }
-    netcsum::BurstPost post{};
-    post.ring = reinterpret_cast<uint64_t>(d_lo - lo);      // the base's alias: offsets count from it
-    post.stride = (uint32_t)stride;
-    post.n = n;
-    post.pkt_len = frame_len;
-    post.spw = spw;
-    post.form = form << 1;
-    post.rx_cfg = rx_cfg;
-    post.eth_cfg = eth_cfg;
-    if (hw_addr != nullptr) {
-        post.have_hw = 1u;
-        post.hw_lo = (uint32_t)hw_addr[0] | ((uint32_t)hw_addr[1] << 8) | ((uint32_t)hw_addr[2] << 16) | ((uint32_t)hw_addr[3] << 24);
-        post.hw_hi = (uint32_t)hw_addr[4] | ((uint32_t)hw_addr[5] << 8);
-    }
-    server_launch_name(form, spw, false);
-    if (h_sums) {
-        e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                                                  *(volatile const uint8_t*)(ha + i) != 0xFFu &&
-                                                                  *(volatile const uint8_t*)(hl + i) != 0xFFu &&
-                                                                  *(volatile const uint32_t*)(hs + 4u * i) != 0xFFFFFFFFu; }, n);
-    } else {
-        e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hf + i) != 0xFFu &&
-                                                                  *(volatile const uint8_t*)(ha + i) != 0xFFu &&
-                                                                  *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
-    }
+    wait.arm(n);
+    b.post.form = b.form << 1;
+    b.post.rx_cfg = rx_cfg;
+    b.post.eth_cfg = eth_cfg;
+    pack_hw_addr(hw_addr, &b.post.have_hw, &b.post.hw_lo, &b.post.hw_hi);
+    server_launch_name(b.form, b.spw, false);
+    e = h_sums ? burst_server_run(t, c, b.post, wait.poll<3, false, true>(), n)
+               : burst_server_run(t, c, b.post, wait.poll<3, false, false>(), n);
     if (e != NET_UTIL_ERR_NONE) return e;
-    if (h_flags) std::memcpy(h_flags, hf, n);
-    std::memcpy(h_action, ha, n);
-    std::memcpy(h_l2, hl, n);
-    if (h_sums) std::memcpy(h_sums, hs, (size_t)n * 4u);
+    if (h_flags) std::memcpy(h_flags, wait.bytes[0], n);
+    std::memcpy(h_action, wait.bytes[1], n);
+    std::memcpy(h_l2, wait.bytes[2], n);
+    if (h_sums) std::memcpy(h_sums, wait.sums, (size_t)n * 4u);
     return NET_UTIL_ERR_NONE;
 }
 
 // RxBurstEther over frames in host memory. A burst from a pinned ring (n_chunks 0, at most 4096 frames in
 // one pinned allocation, TUNE_BURST_ZERO_COPY 3) is served in place by the resident burst server
-// (rx_burst_ether_zero_copy). Every other call: the copy pipeline of pkt_host_copy with the frame-level
-// descriptors (per-frame lengths also without offsets: a ring of slots) and the classes as a third
-// result. Per chunk: H2D of the frames' span and descriptors, the device form (demux, packet batch) on
-// the chunk's stream, D2H of actions, flags and classes.
-// h_sums (RxBurstEtherSumsHost; the entry point has checked it): both stages also return one NETCSUM_FRAG_SUM
-// per frame — the copy pipeline through a fourth result region and the device form RxBurstEtherSums.
+// (rx_burst_ether_zero_copy). Every other call: the copy pipeline with the frame-level descriptors
+// (per-frame lengths also without offsets: a ring of slots) and the classes as a third result. Per chunk:
+// H2D of the frames' span and descriptors, the device form (demux, packet batch) on the chunk's stream,
+// D2H of actions, flags and classes.
+// sums (RxBurstEtherSumsHost): both stages also return one NETCSUM_FRAG_SUM per frame — the copy pipeline
+// through a fourth result region and the device form RxBurstEtherSums.
 static NET_ERR rx_burst_ether_host(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
                                    CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
-                                   const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
+                                   const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2, bool sums,
                                    NETCSUM_FRAG_SUM* h_sums, uint32_t n_chunks) {
-    if (n_frame != 0 && (h_action == nullptr || h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
-    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
+    NET_ERR e = check_rx_ether(h_base, h_action, h_l2, n_frame, rx_cfg, eth_cfg);
+    if (e == NET_UTIL_ERR_NONE && sums) e = check_frag_sums(h_sums, n_frame);
+    if (e != NET_UTIL_ERR_NONE) return e;
     if (n_frame == 0) return NET_UTIL_ERR_NONE;
     if (n_frame > 0x7FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
     HostCtx* cp = nullptr;
-    NET_ERR e = host_ctx(&cp);
+    e = host_ctx(&cp);
     if (e != NET_UTIL_ERR_NONE) return e;
-    HostCtx& c = *cp;
     const Tune& t = tune();
     if (n_chunks == 0 && t.burst_zc == 3) {                  // a burst from a pinned ring: in place
         bool taken = false;
-        e = rx_burst_ether_zero_copy(t, c, h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr,
+        e = rx_burst_ether_zero_copy(t, *cp, h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr,
                                      h_action, h_flags, h_l2, h_sums, &taken);
         if (taken) return e;
     }
-    std::vector<HostChunk> ch;
-    uint64_t maxb = plan_chunks(nullptr, nullptr, stride, frame_len, n_frame, n_chunks == 0 ? 1u : n_chunks, ch);
-    if (h_off != nullptr || h_len != nullptr) {
-        maxb = 0;
-        for (HostChunk& k : ch) {
-            ether_span(h_off, h_len, stride, frame_len, k.s0, k.ns, &k.lo, &k.hi);
-            maxb = std::max<uint64_t>(maxb, k.hi - k.lo);
-        }
-    }
-    const uint32_t per = ch[0].ns;
+    const ChunkPlan plan = plan_chunks(h_off, h_len, stride, frame_len, n_frame, n_chunks);   // (0: one chunk)
+    const size_t per = plan.per;
     // device slot: [bytes | offsets | lengths | flags | actions | classes | fragment sums]; host slot:
     // [offsets | lengths]
-    const size_t o_off = al256(maxb), o_len = o_off + al256(h_off ? (size_t)per * 8u : 0u);
-    const size_t o_fl = o_len + al256(h_len ? (size_t)per * 2u : 0u), o_act = o_fl + al256(per), o_l2 = o_act + al256(per);
-    const size_t o_sum = o_l2 + al256(per);
-    const size_t hs_len = al256(h_off ? (size_t)per * 8u : 0u);
-    e = ensure_pipe(c, o_sum + al256(h_sums ? (size_t)per * sizeof(NETCSUM_FRAG_SUM) : 0u),
-                    hs_len + al256(h_len ? (size_t)per * 2u : 0u));
-    if (e != NET_UTIL_ERR_NONE) return e;
-    PipeDrainOnExit guard{c};
-    const uint8_t* hb = static_cast<const uint8_t*>(h_base);
-    for (size_t k = 0; k < ch.size(); ++k) {
-        const HostChunk& q = ch[k];
-        const int j = (int)(k % 3u);
-        hipStream_t st = c.pstream[j];
-        uint8_t* d = c.d_pipe[j];
-        if (k >= 3 && (h_off || h_len)) NC_HIP(hipStreamSynchronize(st));   // slot j's staging is free again
-        if (q.hi > q.lo) NC_HIP(hipMemcpyAsync(d, hb + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
-        if (h_off) {
-            uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
-            for (uint32_t i = 0; i < q.ns; ++i) h_o[i] = h_off[q.s0 + i] - q.lo;
-            NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
-        }
-        if (h_len) {
-            uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + hs_len);
-            std::memcpy(h_l, h_len + q.s0, (size_t)q.ns * 2u);
-            NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
-        }
+    SlotLayout dev, host;
+    dev.take(plan.max_span);
+    const size_t o_off = dev.take(h_off ? per * 8u : 0u), o_len = dev.take(h_len ? per * 2u : 0u);
+    const size_t o_fl = dev.take(per), o_act = dev.take(per), o_l2 = dev.take(per);
+    const size_t o_sum = dev.take(h_sums ? per * sizeof(NETCSUM_FRAG_SUM) : 0u);
+    const size_t hs_off = host.take(h_off ? per * 8u : 0u), hs_len = host.take(h_len ? per * 2u : 0u);
+    return run_pipe(*cp, plan, dev, host, [&](const HostChunk& q, const PipeSlot& s) -> NET_ERR {
+        uint8_t* d = s.d;
+        NET_ERR e = copy_chunk_bytes(h_base, q, s);
+        if (e == NET_UTIL_ERR_NONE) e = copy_chunk_descriptors(h_off, h_len, q, s, hs_off, o_off, hs_len, o_len);
+        if (e != NET_UTIL_ERR_NONE) return e;
         const uint64_t* d_o = h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr;
         const uint16_t* d_l = h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr;
         if (h_sums) {
             e = NetUtil_MI355X_RxBurstEtherSums(d, d_o, d_l, stride, frame_len, q.ns, rx_cfg, eth_cfg, hw_addr, d + o_act,
                                                 h_flags ? d + o_fl : nullptr, d + o_l2,
-                                                reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum), st);
+                                                reinterpret_cast<NETCSUM_FRAG_SUM*>(d + o_sum), s.st);
         } else {
             e = NetUtil_MI355X_RxBurstEther(d, d_o, d_l, stride, frame_len, q.ns, rx_cfg, eth_cfg, hw_addr, d + o_act,
-                                            h_flags ? d + o_fl : nullptr, d + o_l2, st);
+                                            h_flags ? d + o_fl : nullptr, d + o_l2, s.st);
         }
         if (e != NET_UTIL_ERR_NONE) return e;
-        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
-        NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, st));
-        NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
+        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, s.st));
+        NC_HIP(hipMemcpyAsync(h_action + q.s0, d + o_act, q.ns, hipMemcpyDeviceToHost, s.st));
+        NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, s.st));
         if (h_sums) {
-            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, st));
+            NC_HIP(hipMemcpyAsync(h_sums + q.s0, d + o_sum, (size_t)q.ns * sizeof(NETCSUM_FRAG_SUM), hipMemcpyDeviceToHost, s.st));
         }
-    }
-    for (int j = 0; j < 3; ++j) NC_HIP(hipStreamSynchronize(c.pstream[j]));
-    guard.done = true;
-    return NET_UTIL_ERR_NONE;
+        return NET_UTIL_ERR_NONE;
+    });
 }
 
 NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
@@ -1250,130 +1179,103 @@ NET_ERR NetUtil_MI355X_RxBurstEtherHost(const void* h_base, const uint64_t* h_of
                                         const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
                                         uint32_t n_chunks) {
     return rx_burst_ether_host(h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, h_action, h_flags,
-                               h_l2, nullptr, n_chunks);
+                               h_l2, false, nullptr, n_chunks);
 }
 
-// RxBurstEtherHost's checks in their order, then the records' (RxBurstSumsHost's).
 NET_ERR NetUtil_MI355X_RxBurstEtherSumsHost(const void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
                                             CPU_INT16U frame_len, uint32_t n_frame, uint32_t rx_cfg, uint32_t eth_cfg,
                                             const uint8_t* hw_addr, uint8_t* h_action, uint8_t* h_flags, uint8_t* h_l2,
                                             NETCSUM_FRAG_SUM* h_sums, uint32_t n_chunks) {
-    if (n_frame != 0 && (h_action == nullptr || h_l2 == nullptr || h_base == nullptr)) return NET_ERR_FAULT_NULL_PTR;
-    if (rx_cfg & ~(uint32_t)NETCSUM_RXCFG_UDP_DISCARD_NO_CHK_SUM) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (eth_cfg & ~(uint32_t)NETCSUM_ETHCFG_MCAST_RX) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (n_frame != 0 && h_sums == nullptr) return NET_ERR_FAULT_NULL_PTR;
-    if (((uintptr_t)h_sums & 3u) != 0u || n_frame > 0x3FFFFFFFu) return (NET_ERR)NET_UTIL_ERR_MI355X_INVALID_ARG;
-    if (n_frame == 0) return NET_UTIL_ERR_NONE;
     return rx_burst_ether_host(h_base, h_off, h_len, stride, frame_len, n_frame, rx_cfg, eth_cfg, hw_addr, h_action, h_flags,
-                               h_l2, h_sums, n_chunks);
+                               h_l2, true, h_sums, n_chunks);
 }
-
-static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
-                                   uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
-                                   uint32_t n_chunks);
 
 // A Tx Ether burst over a pinned ring in place, by the resident server's Tx Ether form
 // (netcsum_pktstream.hip pkt_ether_run<TX, REC>): the wave that owns a run classifies its frames by the Tx
 // rule, stores the classes and streams the datagrams in the record-producing Tx instantiation; classes
 // and records arrive in coherent memory behind 0xFF sentinels (no class is >= 16, a record's store byte is
 // 0..3), the host polls both and applies each record at the frame's start + 14, exactly as
-// tx_burst_zero_copy does for datagrams. Nothing on the device writes the ring. Datagrams flagged EXT_HDR
-// (IPv6 chains past the kernel's window) are finished by the copy path as an offset/length batch of those
-// datagrams. Taken under rx_burst_ether_zero_copy's conditions, for a burst tx_burst_zero_copy would accept
-// as an offset/length one (the records come from the run-stream kernel only). *taken = false: the caller
-// takes the copy pipeline.
+// tx_burst_zero_copy does for datagrams. Nothing on the device writes the ring. Taken under
+// ether_burst_setup's conditions, for a burst tx_burst_zero_copy would accept as an offset/length one (the
+// records come from the run-stream kernel only). *taken = false: the caller takes the copy pipeline.
 static NET_ERR tx_burst_ether_zero_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
                                         uint64_t stride, CPU_INT16U frame_len, uint32_t n, uint8_t* h_flags, uint8_t* h_l2,
                                         bool* taken) {
     *taken = false;
-    if (n > kBurstZC || t.kernel == 2) return NET_UTIL_ERR_NONE;
+    if (t.kernel == 2) return NET_UTIL_ERR_NONE;
     const int tb = t.pkt_bound;
     if (tb == 0 || tb == 3) return NET_UTIL_ERR_NONE;        // (offset/length runs: the live-piece forms only)
-    uint64_t lo = 0, hi = 0;
-    ether_span(h_off, h_len, stride, frame_len, 0u, n, &lo, &hi);
-    if (hi <= lo || hi - lo > kBurstZCSpan) return NET_UTIL_ERR_NONE;
-    const uint8_t* d_lo = pinned_alias(static_cast<const uint8_t*>(h_base) + lo, hi - lo);
-    if (d_lo == nullptr) return NET_UTIL_ERR_NONE;
-    *taken = true;
-    NET_ERR e = ensure_burst(c);
+    EtherBurst b;
+    NET_ERR e = ether_burst_setup(c, h_base, h_off, h_len, stride, frame_len, n, &b, taken);
+    if (e != NET_UTIL_ERR_NONE || !*taken) return e;
+    BurstWait wait;
+    wait.bytes[0] = c.h_burst + kBurstL2;
+    wait.rec = c.h_burst + kBurstRec;
+    wait.arm(n);
+    b.post.form = (b.form << 1) | 1u;
+    b.post.udp_mode = 2u;
+    server_launch_name(b.form, b.spw, true);
+    e = burst_server_run(t, c, b.post, wait.poll<1, true, false>(), n);
     if (e != NET_UTIL_ERR_NONE) return e;
-    uint32_t form = netcsum::kBurstEther;
-    const uint32_t spw = server_run(n);                     // (as the offset/length form)
-    if (h_off) {
-        std::memcpy(c.h_burst + kBurstOff, h_off, (size_t)n * 8u);
-        form |= netcsum::kBurstEtherOff;
-    }
-    if (h_len) {
-        std::memcpy(c.h_burst + kBurstLen, h_len, (size_t)n * 2u);
-        form |= netcsum::kBurstEtherLen;
-    }
-    uint8_t* hr = c.h_burst + kBurstRec;
-    uint8_t* hl = c.h_burst + kBurstL2;
-    std::memset(hr, 0xFF, (size_t)n * 8u);
-    std::memset(hl, 0xFF, n);
-    netcsum::BurstPost post{};                              // (every field this form does not use: 0)
-    post.ring = reinterpret_cast<uint64_t>(d_lo - lo);      // the base's alias: offsets count from it
-    post.stride = (uint32_t)stride;
-    post.n = n;
-    post.pkt_len = frame_len;
-    post.spw = spw;
-    post.form = (form << 1) | 1u;
-    post.udp_mode = 2u;
-    server_launch_name(form, spw, true);
-    e = burst_server_run(t, c, post, [&](uint32_t i) { return *(volatile const uint8_t*)(hr + 8u * i + 7u) != 0xFFu &&
-                                                              *(volatile const uint8_t*)(hl + i) != 0xFFu; }, n);
-    if (e != NET_UTIL_ERR_NONE) return e;
-    std::memcpy(h_l2, hl, n);
-    uint8_t* hb = static_cast<uint8_t*>(h_base);
-    const uint64_t* rec = reinterpret_cast<const uint64_t*>(hr);
-    std::vector<uint64_t> walk_off;
-    std::vector<uint16_t> walk_len;
-    std::vector<uint32_t> walk_idx;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t r = rec[i];                          // PktTxRecord: vals | l4_off << 32 | flags << 48 | store << 56
-        const uint32_t flags = (uint32_t)(r >> 48) & 0xFFu, store = (uint32_t)(r >> 56);
-        const uint64_t o = (h_off ? h_off[i] : (uint64_t)i * stride) + NETCSUM_L2_HDR_ETHER;
-        if (flags & NETCSUM_PKT_EXT_HDR) {                  // (only an IP frame's datagram gets this flag)
-            walk_off.push_back(o);
-            walk_len.push_back((uint16_t)((h_len ? h_len[i] : frame_len) - NETCSUM_L2_HDR_ETHER));
-            walk_idx.push_back(i);
-            continue;
-        }
-        uint8_t* p = hb + o;
-        const uint16_t ip = (uint16_t)r, l4 = (uint16_t)(r >> 16);
-        if (store & 1u) std::memcpy(p + 10, &ip, 2);
-        if (store & 2u) std::memcpy(p + ((r >> 32) & 0xFFFFu), &l4, 2);
-        if (h_flags) h_flags[i] = (uint8_t)flags;
-    }
-    if (!walk_off.empty()) {                                // the rare long IPv6 chains: the copy path
-        const uint32_t m = (uint32_t)walk_off.size();
-        std::vector<uint8_t> fl(m);
-        char zc_name[256];
-        snprintf(zc_name, sizeof zc_name, "%s", NetUtil_MI355X_LastLaunch());
-        PktJob rest = pkt_job(h_base, walk_off.data(), walk_len.data(), 0, 0, m, h_flags ? fl.data() : nullptr, nullptr);
-        rest.tx = true;
-        rest.udp_mode = 2u;
-        e = pkt_host_copy(t, rest, 1u);
-        if (e != NET_UTIL_ERR_NONE) return e;
-        char d[256];
-        snprintf(d, sizeof d, "%.180s +copy path for %u EXT_HDR datagrams", zc_name, m);
-        netcsum::set_last_launch(d);
-        if (h_flags) {
-            for (uint32_t k = 0; k < m; ++k) h_flags[walk_idx[k]] = fl[k];
-        }
-    }
-    return NET_UTIL_ERR_NONE;
+    std::memcpy(h_l2, wait.bytes[0], n);
+    const TxSkipped skip = apply_tx_records(reinterpret_cast<const uint64_t*>(wait.rec), static_cast<uint8_t*>(h_base), h_off,
+                                            h_len, stride, frame_len, NETCSUM_L2_HDR_ETHER, n, h_flags);
+    return tx_finish_skipped(t, h_base, skip, 2u, h_flags);
 }
 
-// TxBurstEther over frames in host memory: RxBurstEtherHost's chunk loop (ether_span per chunk) with the Tx
-// return path of pkt_host_copy. Per chunk: H2D of the frames' span and descriptors, the device form on the
-// chunk's copy (Tx demux, the offset/length Tx batch, the field gather over the datagrams' descriptors),
-// D2H of one 8-B record per frame, the classes and the flags; once the chunk's stream has drained the
-// host writes the recorded fields into its own ring at frame + 14 + position. Nothing else of the ring
-// is written. A burst from a pinned ring (n_chunks 0, at most 4096 frames in one pinned allocation,
-// TUNE_BURST_ZERO_COPY 3) is served in place by the resident burst server instead
-// (tx_burst_ether_zero_copy). Checks, their order, error codes and the resulting bytes do not depend on
-// the path.
+// The copy pipeline of TxBurstEtherHost (below): for run_pipe, a slot layout over frame-level descriptors that
+// ends in field positions and records, an issue step and a retire step that applies the records. Per chunk: H2D of the frames' span and descriptors, the device form on the chunk's
+// copy (Tx demux, the offset/length Tx batch, the field gather over the datagrams' descriptors), D2H of the
+// flags, the classes and one 8-B record per frame; once the chunk's stream has drained the host writes the
+// recorded fields into its own ring at frame + 14 + position. Nothing else of the ring is written.
+static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
+                                   uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
+                                   uint32_t n_chunks) {
+    // chunks: TxBurstHost's choice (the host's field write-back overlaps the later chunks' copies)
+    if (n_chunks == 0) n_chunks = std::min(16u, std::max(1u, n_frame / 16384u));
+    if (n_frame / n_chunks > (1u << 28)) n_chunks = (n_frame >> 28) + 1u;
+    const ChunkPlan plan = plan_chunks(h_off, h_len, stride, frame_len, n_frame, n_chunks);
+    const size_t per = plan.per;
+    // device slot: [bytes | offsets | lengths | flags | classes | field positions | records];
+    // host slot: [offsets | lengths | records]
+    SlotLayout dev, host;
+    dev.take(plan.max_span);
+    const size_t o_off = dev.take(h_off ? per * 8u : 0u), o_len = dev.take(h_len ? per * 2u : 0u);
+    const size_t o_fl = dev.take(per), o_l2 = dev.take(per);
+    const size_t o_fp = dev.take(per * 4u), o_rec = dev.take(per * 8u);
+    const size_t hs_off = host.take(h_off ? per * 8u : 0u), hs_len = host.take(h_len ? per * 2u : 0u);
+    const size_t hs_rec = host.take(per * 8u);
+    uint8_t* hb = static_cast<uint8_t*>(h_base);
+    return run_pipe(
+        c, plan, dev, host,
+        [&](const HostChunk& q, const PipeSlot& s) -> NET_ERR {
+            uint8_t* d = s.d;
+            NET_ERR e = copy_chunk_bytes(hb, q, s);
+            if (e == NET_UTIL_ERR_NONE) e = copy_chunk_descriptors(h_off, h_len, q, s, hs_off, o_off, hs_len, o_len);
+            if (e != NET_UTIL_ERR_NONE) return e;
+            uint32_t* d_fp = reinterpret_cast<uint32_t*>(d + o_fp);
+            uint64_t* d_rec = reinterpret_cast<uint64_t*>(d + o_rec);
+            NC_HIP(hipMemsetAsync(d_fp, 0, (size_t)q.ns * 4u, s.st));   // a frame no kernel wrote: no fields
+            // (a strided chunk's copy starts at its first slot: q.lo = s0 * stride, so slot i of the chunk is at i * stride)
+            e = tx_burst_ether(t, d, h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr,
+                               h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr, stride, frame_len, q.ns,
+                               h_flags ? d + o_fl : nullptr, d + o_l2, s.st, d_fp, d_rec);
+            if (e != NET_UTIL_ERR_NONE) return e;
+            if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, s.st));
+            NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, s.st));
+            NC_HIP(hipMemcpyAsync(s.h + hs_rec, d_rec, (size_t)q.ns * 8u, hipMemcpyDeviceToHost, s.st));
+            return NET_UTIL_ERR_NONE;
+        },
+        [&](const HostChunk& q, const PipeSlot& s) {
+            apply_field_records(hb + NETCSUM_L2_HDR_ETHER, h_off, stride, q.s0, q.ns,
+                                reinterpret_cast<const uint64_t*>(s.h + hs_rec));
+        });
+}
+
+// TxBurstEther over frames in host memory. A burst from a pinned ring (n_chunks 0, at most 4096 frames in one
+// pinned allocation, TUNE_BURST_ZERO_COPY 3) is served in place by the resident burst server
+// (tx_burst_ether_zero_copy), every other call by the copy pipeline (tx_burst_ether_copy). Checks, their
+// order, error codes and the resulting bytes do not depend on the path.
 NET_ERR NetUtil_MI355X_TxBurstEtherHost(void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
                                         CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
                                         uint32_t n_chunks) {
@@ -1390,81 +1292,6 @@ NET_ERR NetUtil_MI355X_TxBurstEtherHost(void* h_base, const uint64_t* h_off, con
         if (taken) return e;
     }
     return tx_burst_ether_copy(t, *cp, h_base, h_off, h_len, stride, frame_len, n_frame, h_flags, h_l2, n_chunks);
-}
-
-// The copy pipeline of TxBurstEtherHost (above).
-static NET_ERR tx_burst_ether_copy(const Tune& t, HostCtx& c, void* h_base, const uint64_t* h_off, const uint16_t* h_len,
-                                   uint64_t stride, CPU_INT16U frame_len, uint32_t n_frame, uint8_t* h_flags, uint8_t* h_l2,
-                                   uint32_t n_chunks) {
-    NET_ERR e = NET_UTIL_ERR_NONE;
-    // chunks: TxBurstHost's choice (the host's field write-back overlaps the later chunks' copies)
-    if (n_chunks == 0) n_chunks = std::min(16u, std::max(1u, n_frame / 16384u));
-    if (n_frame / n_chunks > (1u << 28)) n_chunks = (n_frame >> 28) + 1u;
-    std::vector<HostChunk> ch;
-    uint64_t maxb = plan_chunks(nullptr, nullptr, stride, frame_len, n_frame, n_chunks, ch);
-    if (h_off != nullptr || h_len != nullptr) {
-        maxb = 0;
-        for (HostChunk& k : ch) {
-            ether_span(h_off, h_len, stride, frame_len, k.s0, k.ns, &k.lo, &k.hi);
-            maxb = std::max<uint64_t>(maxb, k.hi > k.lo ? k.hi - k.lo : 0u);
-        }
-    }
-    const uint32_t per = ch[0].ns;
-    // device slot: [bytes | offsets | lengths | flags | classes | field positions | records];
-    // host slot: [offsets | lengths | records]
-    const size_t o_off = al256(maxb), o_len = o_off + al256(h_off ? (size_t)per * 8u : 0u);
-    const size_t o_fl = o_len + al256(h_len ? (size_t)per * 2u : 0u), o_l2 = o_fl + al256(per);
-    const size_t o_fp = o_l2 + al256(per), o_rec = o_fp + al256((size_t)per * 4u);
-    const size_t hs_len = al256(h_off ? (size_t)per * 8u : 0u);
-    const size_t hs_rec = hs_len + al256(h_len ? (size_t)per * 2u : 0u);
-    e = ensure_pipe(c, o_rec + al256((size_t)per * 8u), hs_rec + (size_t)per * 8u);
-    if (e != NET_UTIL_ERR_NONE) return e;
-    PipeDrainOnExit guard{c};
-    uint8_t* hb = static_cast<uint8_t*>(h_base);
-    auto drain = [&](size_t k) -> NET_ERR {                  // chunk k's stream has finished: apply its records
-        NC_HIP(hipStreamSynchronize(c.pstream[k % 3u]));
-        apply_field_records(hb + NETCSUM_L2_HDR_ETHER, h_off, stride, ch[k].s0, ch[k].ns,
-                            reinterpret_cast<const uint64_t*>(c.h_pipe[k % 3u] + hs_rec));
-        return NET_UTIL_ERR_NONE;
-    };
-    for (size_t k = 0; k < ch.size(); ++k) {
-        const HostChunk& q = ch[k];
-        const int j = (int)(k % 3u);
-        hipStream_t st = c.pstream[j];
-        uint8_t* d = c.d_pipe[j];
-        if (k >= 3) {                                        // slot j's staging is free again
-            e = drain(k - 3u);
-            if (e != NET_UTIL_ERR_NONE) return e;
-        }
-        if (q.hi > q.lo) NC_HIP(hipMemcpyAsync(d, hb + q.lo, q.hi - q.lo, hipMemcpyHostToDevice, st));
-        if (h_off) {
-            uint64_t* h_o = reinterpret_cast<uint64_t*>(c.h_pipe[j]);
-            for (uint32_t i = 0; i < q.ns; ++i) h_o[i] = h_off[q.s0 + i] - q.lo;
-            NC_HIP(hipMemcpyAsync(d + o_off, h_o, (size_t)q.ns * 8u, hipMemcpyHostToDevice, st));
-        }
-        if (h_len) {
-            uint16_t* h_l = reinterpret_cast<uint16_t*>(c.h_pipe[j] + hs_len);
-            std::memcpy(h_l, h_len + q.s0, (size_t)q.ns * 2u);
-            NC_HIP(hipMemcpyAsync(d + o_len, h_l, (size_t)q.ns * 2u, hipMemcpyHostToDevice, st));
-        }
-        uint32_t* d_fp = reinterpret_cast<uint32_t*>(d + o_fp);
-        uint64_t* d_rec = reinterpret_cast<uint64_t*>(d + o_rec);
-        NC_HIP(hipMemsetAsync(d_fp, 0, (size_t)q.ns * 4u, st));   // a frame no kernel wrote: no fields
-        // (a strided chunk's copy starts at its first slot: q.lo = s0 * stride, so slot i of the chunk is at i * stride)
-        e = tx_burst_ether(t, d, h_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr,
-                           h_len ? reinterpret_cast<const uint16_t*>(d + o_len) : nullptr, stride, frame_len, q.ns,
-                           h_flags ? d + o_fl : nullptr, d + o_l2, st, d_fp, d_rec);
-        if (e != NET_UTIL_ERR_NONE) return e;
-        if (h_flags) NC_HIP(hipMemcpyAsync(h_flags + q.s0, d + o_fl, q.ns, hipMemcpyDeviceToHost, st));
-        NC_HIP(hipMemcpyAsync(h_l2 + q.s0, d + o_l2, q.ns, hipMemcpyDeviceToHost, st));
-        NC_HIP(hipMemcpyAsync(c.h_pipe[j] + hs_rec, d_rec, (size_t)q.ns * 8u, hipMemcpyDeviceToHost, st));
-    }
-    for (size_t k = ch.size() > 3 ? ch.size() - 3 : 0; k < ch.size(); ++k) {
-        e = drain(k);
-        if (e != NET_UTIL_ERR_NONE) return e;
-    }
-    guard.done = true;
-    return NET_UTIL_ERR_NONE;
 }
 
 NET_ERR NetUtil_MI355X_TxBurstHost(void* h_base, const uint64_t* h_off, const uint16_t* h_len, uint64_t stride,
