@@ -23,6 +23,7 @@
  * stdout. With the argument "txether": the Tx Ether mode (tx_ether_only below), TxBurstEtherHost on the
  * same slots against TxBurstHost at +14. With "ethersums" (and optionally "frag"): the fragment-sums mode
  * (ether_sums_only below), RxBurstEtherSumsHost against RxBurstEtherHost and RxBurstSumsHost on the same ring.
+ * With "short": the default mode for 1, 64 and 1024 frames only.
  *
  * Built here (the binary travels with the tree; tools/build/ is git-ignored), run on the GPU box:
  *   gcc -O2 -std=c11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tools/burst_latency.c \
@@ -349,7 +350,11 @@ static int ether_sums_only(int frag)
 
 int main(int argc, char **argv)
 {
-    static const uint32_t sizes[] = {1u, 10u, 16u, 32u, 64u, 128u, 256u, 1024u, 4096u, 16384u, 65536u, 262144u};
+    static const uint32_t all_sizes[] = {1u, 10u, 16u, 32u, 64u, 128u, 256u, 1024u, 4096u, 16384u, 65536u, 262144u};
+    static const uint32_t short_sizes[] = {1u, 64u, 1024u};
+    const int brief = argc > 1 && strcmp(argv[1], "short") == 0;
+    const uint32_t *sizes = brief ? short_sizes : all_sizes;
+    const size_t n_sizes = brief ? sizeof short_sizes / sizeof short_sizes[0] : sizeof all_sizes / sizeof all_sizes[0];
     const size_t bytes = (size_t)NMAX * SLOT;
     uint32_t i, s;
     HIP_OK(hipSetDevice(0));
@@ -369,7 +374,7 @@ int main(int argc, char **argv)
     if (argc > 1 && strcmp(argv[1], "zc") == 0) return zc_only();
     if (argc > 1 && strcmp(argv[1], "txether") == 0) return tx_ether_only();
     if (argc > 1 && strcmp(argv[1], "ethersums") == 0) return ether_sums_only(argc > 2 && strcmp(argv[2], "frag") == 0);
-    for (s = 0; s < sizeof sizes / sizeof sizes[0]; ++s) {
+    for (s = 0; s < n_sizes; ++s) {
         const uint32_t n = sizes[s];
         double rx_dev, tx_dev, rx_host, tx_host;
         int ok = 1, z;

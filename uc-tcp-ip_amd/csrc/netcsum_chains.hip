@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "netcsum_device.h"
+#include "netcsum_dispatch.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
 
@@ -861,15 +862,12 @@ hipError_t launch_chain_two_pass_h(const KernelTune& k, const ChainBatchArgs& a,
                                    hipStream_t s, uint32_t spw, int depth, bool cmp, int combine_lanes) {
     hipError_t e = launch_chain_live_records(k, a, rec, cap, depth, spw, cmp, s);
     if (e != hipSuccess) return e;
-    const uint32_t cg = combine_lanes == 64 ? 64u : 16u;
-    const uint64_t blocks = ((uint64_t)a.n + 256u / cg - 1u) / (256u / cg);
-    const unsigned g2 = (unsigned)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1) * 64u);
-    if (cg == 64u) {
-        hipLaunchKernelGGL(chain_combine_h_kernel<64>, dim3(g2), dim3(256), 0, s, a, (const uint32_t*)rec, cap);
-    } else {
-        hipLaunchKernelGGL(chain_combine_h_kernel<16>, dim3(g2), dim3(256), 0, s, a, (const uint32_t*)rec, cap);
-    }
-    return hipGetLastError();
+    return dsp::pick(hipErrorInvalidValue, [&](auto cg) {         // 64 lanes per chain, else 16
+        const uint64_t blocks = ((uint64_t)a.n + 256u / cg - 1u) / (256u / cg);
+        const unsigned g2 = (unsigned)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1) * 64u);
+        hipLaunchKernelGGL(chain_combine_h_kernel<cg>, dim3(g2), dim3(256), 0, s, a, (const uint32_t*)rec, cap);
+        return hipGetLastError();
+    }, dsp::Or<16, 64>{combine_lanes});
 }
 
 hipError_t launch_chain_two_pass(const KernelTune& k, const ChainBatchArgs& a, uint64_t* eo, uint32_t cap, int cus, hipStream_t s,
@@ -877,12 +875,10 @@ hipError_t launch_chain_two_pass(const KernelTune& k, const ChainBatchArgs& a, u
     if (live_spw != 0u) {                                          // pass 1 in the live-sector stream:
         const uint64_t waves = ((uint64_t)cap + live_spw - 1u) / live_spw;   // a wave per run of the most
         const dim3 g1((unsigned)((waves + 3u) / 4u));              // pieces the records hold; runs past
-        if (live_depth == 4) {                                     // the batch's return at once
-            hipLaunchKernelGGL(chain_live_piece_kernel<4>, g1, dim3(256), 0, s, a, eo, cap, live_spw);
-        } else {
-            hipLaunchKernelGGL(chain_live_piece_kernel<8>, g1, dim3(256), 0, s, a, eo, cap, live_spw);
-        }
-        hipError_t e = hipGetLastError();
+        const hipError_t e = dsp::pick(hipErrorInvalidValue, [&](auto d) {   // the batch's return at once
+            hipLaunchKernelGGL(chain_live_piece_kernel<d>, g1, dim3(256), 0, s, a, eo, cap, live_spw);
+            return hipGetLastError();
+        }, dsp::Or<8, 4>{live_depth});
         if (e != hipSuccess) return e;
         const uint64_t blocks = ((uint64_t)a.n + 15u) / 16u;
         const unsigned g2 = (unsigned)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1) * 64u);
@@ -927,19 +923,12 @@ hipError_t launch_chain_two_pass(const KernelTune& k, const ChainBatchArgs& a, u
 }
 
 hipError_t launch_chain_batch(const ChainBatchArgs& a, int group, int grid, hipStream_t s) {
-    switch (group) {
-    case 16:
-        hipLaunchKernelGGL(chain_batch_kernel<16>, dim3(grid), dim3(256), 0, s, a);
-        break;
-    case 32:
-        hipLaunchKernelGGL(chain_batch_kernel<32>, dim3(grid), dim3(256), 0, s, a);
-        break;
-    case 64:
-        hipLaunchKernelGGL(chain_batch_kernel<64>, dim3(grid), dim3(256), 0, s, a);
-        break;
-    default:
+    const bool grouped = dsp::pick(false, [&](auto g) {          // group 16, 32 or 64, else a wave per chain
+        hipLaunchKernelGGL(chain_batch_kernel<g>, dim3(grid), dim3(256), 0, s, a);
+        return true;
+    }, dsp::Of<16, 32, 64>{group});
+    if (!grouped) {
         hipLaunchKernelGGL(chain_wave_kernel, dim3(grid), dim3(256), 0, s, a);
-        break;
     }
     return hipGetLastError();
 }

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "netcsum_device.h"
+#include "netcsum_dispatch.h"
 #include "netcsum_kernels.h"
 
 namespace netcsum {
@@ -703,7 +704,7 @@ uint32_t h_x8n(uint64_t n) {
     return p;
 }
 
-enum class CrcForm { Lane, Block, Ilv1, Ilv2, Ilv4, Ilv8, Ilv16 };
+enum class CrcForm { Lane = -1, Block = 0, Ilv1 = 1, Ilv2 = 2, Ilv4 = 4, Ilv8 = 8, Ilv16 = 16 };   // IlvG: G lanes
 
 CrcForm ilv_form(const KernelTune& k, uint32_t max_len, bool varlen) {
     switch (k.crc_lanes) {
@@ -756,28 +757,16 @@ const char* crc_launch_name(const KernelTune& k, uint32_t max_len, bool varlen) 
     }
 }
 
-template <int G, int W>
-static void launch_ilv_w(const KernelTune& k, const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
+template <int G, int W, bool NT>
+static hipError_t launch_ilv(const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
     constexpr uint32_t B = ilv_block(W);
     const uint32_t steps = (a.n + (B / G) - 1u) / (B / G);
     // blocks resident per CU by LDS: byte tables 24 / 20 / <= 16 KiB (256 threads); W 1 44 .. 60 KiB
     // (512); W 2 85 .. 97 KiB (1024)
     const uint32_t per_cu = W == 2 ? 1u : W == 1 ? (G >= 8 ? 2u : 3u) : (G == 16 ? 6u : G == 8 ? 8u : 10u);
     const uint32_t grid = std::min<uint32_t>(steps, cu * per_cu);
-    if (k.crc_nt) {
-        hipLaunchKernelGGL((crc_ilv_kernel<G, true, W>), dim3(grid), dim3(B), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((crc_ilv_kernel<G, false, W>), dim3(grid), dim3(B), 0, s, a);
-    }
-}
-
-template <int G>
-static void launch_ilv(const KernelTune& k, const CrcBatchArgs& a, uint32_t cu, hipStream_t s) {
-    switch (k.crc_wide) {
-    case 0: launch_ilv_w<G, 0>(k, a, cu, s); break;
-    case 2: launch_ilv_w<G, 2>(k, a, cu, s); break;
-    default: launch_ilv_w<G, 1>(k, a, cu, s); break;
-    }
+    hipLaunchKernelGGL((crc_ilv_kernel<G, NT, W>), dim3(grid), dim3(B), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_crc_batch(const KernelTune& k, const CrcBatchArgs& a0, uint32_t max_len, int cus, hipStream_t s) {
@@ -785,7 +774,8 @@ hipError_t launch_crc_batch(const KernelTune& k, const CrcBatchArgs& a0, uint32_
     CrcBatchArgs a = a0;
     const uint32_t cu = (uint32_t)std::max(1, cus);
     const bool varlen = a.lens != nullptr;
-    switch (crc_form(k, max_len, varlen)) {
+    const CrcForm form = crc_form(k, max_len, varlen);
+    switch (form) {
     case CrcForm::Lane: {
         const uint32_t grid = std::min<uint32_t>((a.n + 255u) / 256u, cu * 8u);   // LDS 4 KiB per block
         if (!varlen && a.off == nullptr && a.len <= 16u) {
@@ -809,11 +799,9 @@ hipError_t launch_crc_batch(const KernelTune& k, const CrcBatchArgs& a0, uint32_
         hipLaunchKernelGGL(crc_group_kernel, dim3(std::min<uint32_t>(steps, cu * 8u)), dim3(256), 0, s, a);
         break;
     }
-    case CrcForm::Ilv1: launch_ilv<1>(k, a, cu, s); break;
-    case CrcForm::Ilv2: launch_ilv<2>(k, a, cu, s); break;
-    case CrcForm::Ilv4: launch_ilv<4>(k, a, cu, s); break;
-    case CrcForm::Ilv8: launch_ilv<8>(k, a, cu, s); break;
-    default: launch_ilv<16>(k, a, cu, s); break;
+    default:                                                  // IlvG; crc_wide 0 or 2, else 1
+        return dsp::pick(hipErrorInvalidValue, [&](auto g, auto w, auto nt) { return launch_ilv<g, w, nt>(a, cu, s); },
+                         dsp::Or<16, 1, 2, 4, 8>{(int)form}, dsp::Or<1, 0, 2>{k.crc_wide}, dsp::Flag{k.crc_nt != 0});
     }
     return hipGetLastError();
 }

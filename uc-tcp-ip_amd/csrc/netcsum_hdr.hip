@@ -35,6 +35,7 @@
 
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
+#include "netcsum_tables.h"
 
 namespace netcsum {
 
@@ -201,38 +202,31 @@ int hdr_lanes_h(const SegBatchArgs& a, int h) {
     return h;
 }
 
-#define NETCSUM_HDR_LIST(X) \
-    X(1, 2, 1) X(1, 3, 1) X(1, 4, 1) X(2, 2, 1) X(2, 3, 1) X(2, 4, 1) X(3, 2, 1) X(3, 3, 1) X(3, 4, 1) \
-    X(4, 2, 1) X(4, 3, 1) X(4, 4, 1) X(5, 2, 1) X(5, 3, 1) X(5, 4, 1)                                  \
-    X(1, 2, 2) X(1, 3, 2) X(1, 4, 2) X(2, 2, 2) X(2, 3, 2) X(2, 4, 2) X(3, 2, 2) X(3, 3, 2) X(3, 4, 2) \
-    X(4, 2, 2) X(4, 3, 2) X(4, 4, 2) X(5, 2, 2) X(5, 3, 2) X(5, 4, 2) X(6, 2, 2) X(6, 3, 2) X(6, 4, 2) \
-    X(1, 2, 4) X(1, 3, 4) X(2, 2, 4) X(2, 3, 4) X(3, 2, 4) X(3, 3, 4) X(4, 2, 4) X(4, 3, 4)            \
-    X(5, 2, 4) X(5, 3, 4) X(6, 2, 4) X(6, 3, 4)
+namespace {
+
+// seg_hdr_kernel's instantiation for the batch: f(P, S, H), for the launch and the occupancy query
+// alike; miss where HdrTable has no such tile.
+template <typename R, typename F>
+R with_hdr_kernel(const SegBatchArgs& a, int stages, int h, R miss, F&& f) {
+    h = hdr_lanes_h(a, h);
+    return dsp::pick_tuple(HdrTable{}, miss, f, hdr_pieces(a, h), hdr_stages(stages, h), h);
+}
+
+}  // namespace
 
 // Resident 256-thread blocks per CU. stages 2..4 (H = 4: 2..3).
 int hdr_occupancy(const SegBatchArgs& a, int stages, int h) {
-    h = hdr_lanes_h(a, h);
-    const uint32_t p = hdr_pieces(a, h);
-    const int S = std::min(stages == 3 ? 3 : (stages == 4 ? 4 : 2), h == 4 ? 3 : 4);
-    int occ = 0;
-    hipError_t e = hipErrorInvalidValue;
-#define NETCSUM_H(P_, S_, H_) \
-    if (p == P_ && S == S_ && h == H_) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, seg_hdr_kernel<P_, S_, H_>, 256, 0);
-    NETCSUM_HDR_LIST(NETCSUM_H)
-#undef NETCSUM_H
-    return (e == hipSuccess && occ > 0) ? occ : 1;
+    return with_hdr_kernel(a, stages, h, 1, [](auto p, auto st, auto hh) {
+        int occ = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, seg_hdr_kernel<p, st, hh>, 256, 0);
+        return (e == hipSuccess && occ > 0) ? occ : 1;
+    });
 }
 
 hipError_t launch_hdr_batch(const SegBatchArgs& a, int stages, int h, int grid, hipStream_t s) {
     if (!hdr_supported(a)) return hipErrorInvalidValue;
-    h = hdr_lanes_h(a, h);
-    const uint32_t p = hdr_pieces(a, h);
-    const int S = std::min(stages == 3 ? 3 : (stages == 4 ? 4 : 2), h == 4 ? 3 : 4);
-#define NETCSUM_H(P_, S_, H_) \
-    if (p == P_ && S == S_ && h == H_) return launch_hdr_t<P_, S_, H_>(a, grid, s);
-    NETCSUM_HDR_LIST(NETCSUM_H)
-#undef NETCSUM_H
-    return hipErrorInvalidValue;
+    return with_hdr_kernel(a, stages, h, hipErrorInvalidValue,
+                           [&](auto p, auto st, auto hh) { return launch_hdr_t<p, st, hh>(a, grid, s); });
 }
 
 }  // namespace netcsum

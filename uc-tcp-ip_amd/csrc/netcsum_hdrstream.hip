@@ -23,6 +23,7 @@
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
+#include "netcsum_tables.h"
 
 namespace netcsum {
 
@@ -154,18 +155,14 @@ __global__ void __launch_bounds__(256) seg_hdrstream_kernel(SegBatchArgs A, uint
     touch_retire(touch);
 }
 
-template <int M, int D, bool NT>
+template <int M, int D, bool NT, bool BURST>
 hipError_t launch_hs_t(const KernelTune& k, const SegBatchArgs& a0, uint32_t spw, hipStream_t s) {
     SegBatchArgs a = a0;
     a.touch = stream_touch(k, true) ? 1u : 0u;
     a.xcd = stream_xcd(k, false) ? 1u : 0u;   // r2x: 0.0579-0.0584 ms off vs 0.0589 on
     const uint64_t waves = ((uint64_t)a.n_seg + spw - 1u) / spw;
     const dim3 grid((unsigned)((waves + 3u) / 4u));
-    if (hdr_burst(k)) {
-        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
-    } else {
-        hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, false>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
-    }
+    hipLaunchKernelGGL((seg_hdrstream_kernel<M, D, NT, BURST>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
     return hipGetLastError();
 }
 
@@ -180,13 +177,9 @@ bool hdrstream_supported(const SegBatchArgs& a) {
 
 hipError_t launch_hdrstream(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
     if (!hdrstream_supported(a) || spw == 0u || spw > (1u << 20)) return hipErrorInvalidValue;
-    const int m = (int)(a.seg_len / 4u);
-#define NETCSUM_HS(M_, D_, NT_) \
-    if (m == M_ && depth == D_ && nt == NT_) return launch_hs_t<M_, D_, NT_>(k, a, spw, s);
-    NETCSUM_HS(5, 4, true) NETCSUM_HS(5, 4, false) NETCSUM_HS(5, 8, true) NETCSUM_HS(5, 8, false)
-    NETCSUM_HS(4, 4, true) NETCSUM_HS(4, 4, false) NETCSUM_HS(4, 8, true) NETCSUM_HS(4, 8, false)
-#undef NETCSUM_HS
-    return hipErrorInvalidValue;
+    return dsp::pick(hipErrorInvalidValue, [&](auto m, auto d, auto ntc, auto burst) {
+        return launch_hs_t<m, d, ntc, burst>(k, a, spw, s);
+    }, dsp::Of<5, 4>{a.seg_len / 4u}, LiveDepth{depth}, dsp::Flag{nt}, dsp::Flag{hdr_burst(k)});
 }
 
 }  // namespace netcsum

@@ -35,6 +35,7 @@
 
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
+#include "netcsum_tables.h"
 
 namespace netcsum {
 
@@ -820,102 +821,29 @@ static int pick_grid(Kern kern, const LaunchCfg& c) {
     return (int)(g ? g : 1);
 }
 
-template <int G, int K, bool VARLEN, bool NT>
-static hipError_t launch_seg(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
-    const int grid = pick_grid(seg_batch_kernel<G, K, VARLEN, NT>, c);
-    hipLaunchKernelGGL((seg_batch_kernel<G, K, VARLEN, NT>), dim3(grid), dim3(c.block), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int G, int K, bool VARLEN>
-static hipError_t launch_seg_nt(const SegBatchArgs& a, const LaunchCfg& c, bool nt, hipStream_t s) {
-    return nt ? launch_seg<G, K, VARLEN, true>(a, c, s)
-              : launch_seg<G, K, VARLEN, false>(a, c, s);
-}
-
-template <int G, bool VARLEN>
-static hipError_t launch_seg_k(const SegBatchArgs& a, int k, const LaunchCfg& c, bool nt, hipStream_t s) {
-    switch (k) {
-    case 1:  return launch_seg_nt<G, 1, VARLEN>(a, c, nt, s);
-    case 2:  return launch_seg_nt<G, 2, VARLEN>(a, c, nt, s);
-    case 3:  return launch_seg_nt<G, 3, VARLEN>(a, c, nt, s);
-    default: return launch_seg_nt<G, 4, VARLEN>(a, c, nt, s);
+// The lane-group kernels 1 (one pass), 2 (pipe) and 3 (LDS) of one (G, K, VARLEN, NT).
+template <int KID, int G, int K, bool VARLEN, bool NT>
+static constexpr auto lane_group_kernel() {
+    if constexpr (KID == 1) {
+        return seg_batch_kernel<G, K, VARLEN, NT>;
+    } else if constexpr (KID == 2) {
+        return seg_pipe_kernel<G, K, VARLEN, NT>;
+    } else {
+        return seg_lds_kernel<G, K, VARLEN, NT>;
     }
 }
 
-template <bool VARLEN>
-static hipError_t launch_seg_g(const SegBatchArgs& a, int g, int k, const LaunchCfg& c, bool nt,
-                               hipStream_t s) {
-    switch (g) {
-    case 1:  return launch_seg_k<1, VARLEN>(a, k, c, nt, s);
-    case 4:  return launch_seg_k<4, VARLEN>(a, k, c, nt, s);
-    case 8:  return launch_seg_k<8, VARLEN>(a, k, c, nt, s);
-    case 16: return launch_seg_k<16, VARLEN>(a, k, c, nt, s);
-    case 32: return launch_seg_k<32, VARLEN>(a, k, c, nt, s);
-    default: return launch_seg_k<64, VARLEN>(a, k, c, nt, s);
-    }
-}
-
-template <int G, int K, bool VARLEN, bool NT>
-static hipError_t launch_pipe(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
-    const int grid = pick_grid(seg_pipe_kernel<G, K, VARLEN, NT>, c);
-    hipLaunchKernelGGL((seg_pipe_kernel<G, K, VARLEN, NT>), dim3(grid), dim3(c.block), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int G, bool VARLEN, bool NT>
-static hipError_t launch_pipe_k(const SegBatchArgs& a, int k, const LaunchCfg& c, hipStream_t s) {
-    switch (k) {
-    case 1:  return launch_pipe<G, 1, VARLEN, NT>(a, c, s);
-    case 2:  return launch_pipe<G, 2, VARLEN, NT>(a, c, s);
-    case 3:  return launch_pipe<G, 3, VARLEN, NT>(a, c, s);
-    case 4:  return launch_pipe<G, 4, VARLEN, NT>(a, c, s);
-    case 6:  return launch_pipe<G, 6, VARLEN, NT>(a, c, s);
-    default: return launch_pipe<G, 8, VARLEN, NT>(a, c, s);
-    }
-}
-
-template <bool VARLEN, bool NT>
-static hipError_t launch_pipe_g(const SegBatchArgs& a, int g, int k, const LaunchCfg& c, hipStream_t s) {
-    switch (g) {
-    case 1:  return launch_pipe_k<1, VARLEN, NT>(a, k, c, s);
-    case 4:  return launch_pipe_k<4, VARLEN, NT>(a, k, c, s);
-    case 8:  return launch_pipe_k<8, VARLEN, NT>(a, k, c, s);
-    case 16: return launch_pipe_k<16, VARLEN, NT>(a, k, c, s);
-    case 32: return launch_pipe_k<32, VARLEN, NT>(a, k, c, s);
-    default: return launch_pipe_k<64, VARLEN, NT>(a, k, c, s);
-    }
-}
-
-template <int G, int K, bool VARLEN, bool NT>
-static hipError_t launch_lds(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
-    const int grid = pick_grid(seg_lds_kernel<G, K, VARLEN, NT>, c);
-    hipLaunchKernelGGL((seg_lds_kernel<G, K, VARLEN, NT>), dim3(grid), dim3(c.block), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int G, bool VARLEN, bool NT>
-static hipError_t launch_lds_k(const SegBatchArgs& a, int k, const LaunchCfg& c, hipStream_t s) {
-    switch (k) {
-    case 1:  return launch_lds<G, 1, VARLEN, NT>(a, c, s);
-    case 2:  return launch_lds<G, 2, VARLEN, NT>(a, c, s);
-    case 3:  return launch_lds<G, 3, VARLEN, NT>(a, c, s);
-    case 4:  return launch_lds<G, 4, VARLEN, NT>(a, c, s);
-    case 6:  return launch_lds<G, 6, VARLEN, NT>(a, c, s);
-    default: return launch_lds<G, 8, VARLEN, NT>(a, c, s);
-    }
-}
-
-template <bool VARLEN, bool NT>
-static hipError_t launch_lds_g(const SegBatchArgs& a, int g, int k, const LaunchCfg& c, hipStream_t s) {
-    switch (g) {
-    case 1:  return launch_lds_k<1, VARLEN, NT>(a, k, c, s);
-    case 4:  return launch_lds_k<4, VARLEN, NT>(a, k, c, s);
-    case 8:  return launch_lds_k<8, VARLEN, NT>(a, k, c, s);
-    case 16: return launch_lds_k<16, VARLEN, NT>(a, k, c, s);
-    case 32: return launch_lds_k<32, VARLEN, NT>(a, k, c, s);
-    default: return launch_lds_k<64, VARLEN, NT>(a, k, c, s);
-    }
+// G is one of 1, 4, 8, 16, 32, else 64; K one of 1, 2, 3, else 4 (one pass), or of 1, 2, 3, 4, 6, else 8.
+template <int KID>
+static hipError_t launch_lane_group(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
+    using Chunks = std::conditional_t<KID == 1, dsp::Or<4, 1, 2, 3>, dsp::Or<8, 1, 2, 3, 4, 6>>;
+    return dsp::pick(hipErrorInvalidValue, [&](auto g, auto k, auto varlen, auto nt) {
+        const auto kern = lane_group_kernel<KID, g, k, varlen, nt>();
+        const int grid = pick_grid(kern, c);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(c.block), 0, s, a);
+        return hipGetLastError();
+    }, dsp::Or<64, 1, 4, 8, 16, 32>{c.group_lanes}, Chunks{c.chunks_per_pass}, dsp::Flag{a.seg_off != nullptr},
+       dsp::Flag{c.nt});
 }
 
 template <int G, int P, int K, bool NT>
@@ -936,26 +864,14 @@ static hipError_t launch_tile(const SegBatchArgs& a, const LaunchCfg& c, hipStre
     return hipGetLastError();
 }
 
-// The v4 instantiations: (G lanes per segment, P KiB image pieces, K chunks per lane).
-#define NETCSUM_TILE_TABLE(X)                                                                       \
-    X(1, 2, 3) X(1, 4, 6) X(4, 1, 1) X(4, 2, 2) X(8, 2, 2) X(8, 4, 4) X(16, 4, 4) X(16, 6, 6)       \
-    X(16, 8, 8) X(32, 2, 2) X(32, 4, 3) X(32, 4, 4) X(32, 8, 8) X(64, 2, 2) X(64, 4, 4) X(64, 8, 8)
-
 bool tile_supported(int g, int p, int k) {
-#define X(G_, P_, K_) if (g == G_ && p == P_ && k == K_) return true;
-    NETCSUM_TILE_TABLE(X)
-#undef X
-    return false;
+    return dsp::pick_tuple(TileTable{}, false, [](auto, auto, auto) { return true; }, g, p, k);
 }
 
 static hipError_t launch_tile_dispatch(const SegBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
-#define X(G_, P_, K_)                                                                                \
-    if (c.group_lanes == G_ && c.tile_pieces == P_ && c.chunks_per_pass == K_) {                     \
-        return c.nt ? launch_tile<G_, P_, K_, true>(a, c, s) : launch_tile<G_, P_, K_, false>(a, c, s); \
-    }
-    NETCSUM_TILE_TABLE(X)
-#undef X
-    return hipErrorInvalidValue;
+    return dsp::pick_tuple(TileTable{}, hipErrorInvalidValue, [&](auto g, auto p, auto k) {
+        return dsp::pick(hipErrorInvalidValue, [&](auto nt) { return launch_tile<g, p, k, nt>(a, c, s); }, dsp::Flag{c.nt});
+    }, c.group_lanes, c.tile_pieces, c.chunks_per_pass);
 }
 
 thread_local char g_last_launch[256];
@@ -979,8 +895,7 @@ static void note_launch(const KernelTune& k, const LaunchCfg& c, const SegBatchA
     }
     if (kid == 7) {
         const int h = hdr_lanes_h(a, c.tile);
-        const int st = c.chunks_per_pass;                         // as launch_hdr_batch resolves it
-        const int S = std::min(st == 3 ? 3 : (st == 4 ? 4 : 2), h == 4 ? 3 : 4);
+        const int S = hdr_stages(c.chunks_per_pass, h);
         const uint32_t tiles = (a.n_seg + 64u * h - 1u) / (64u * h);
         const uint32_t g = c.grid > 0 ? (uint32_t)c.grid : (tiles + 15u) / 16u;
         snprintf(g_last_launch, sizeof(g_last_launch), "seg_hdr_kernel<P=%u,S=%d,H=%d> block=256 grid=%u",
@@ -1025,24 +940,12 @@ hipError_t launch_seg_batch(const KernelTune& k, const SegBatchArgs& args, const
         return launch_tile_dispatch(a, c, s);
     }
     if (c.kernel == 3) {
-        if (a.seg_off) {
-            return c.nt ? launch_lds_g<true, true>(a, c.group_lanes, c.chunks_per_pass, c, s)
-                        : launch_lds_g<true, false>(a, c.group_lanes, c.chunks_per_pass, c, s);
-        }
-        return c.nt ? launch_lds_g<false, true>(a, c.group_lanes, c.chunks_per_pass, c, s)
-                    : launch_lds_g<false, false>(a, c.group_lanes, c.chunks_per_pass, c, s);
+        return launch_lane_group<3>(a, c, s);
     }
     if (c.kernel == 2) {
-        if (a.seg_off) {
-            return c.nt ? launch_pipe_g<true, true>(a, c.group_lanes, c.chunks_per_pass, c, s)
-                        : launch_pipe_g<true, false>(a, c.group_lanes, c.chunks_per_pass, c, s);
-        }
-        return c.nt ? launch_pipe_g<false, true>(a, c.group_lanes, c.chunks_per_pass, c, s)
-                    : launch_pipe_g<false, false>(a, c.group_lanes, c.chunks_per_pass, c, s);
+        return launch_lane_group<2>(a, c, s);
     }
-    const int chunks = c.chunks_per_pass > 4 ? 4 : c.chunks_per_pass;
-    return a.seg_off ? launch_seg_g<true>(a, c.group_lanes, chunks, c, c.nt, s)
-                     : launch_seg_g<false>(a, c.group_lanes, chunks, c, c.nt, s);
+    return launch_lane_group<1>(a, c, s);
 }
 
 hipError_t launch_stream_exact(const void* d_p, uint32_t n16, unsigned long long* d_sum, int grid,
@@ -1062,24 +965,12 @@ hipError_t launch_fill(void* d_buf, uint64_t n_bytes, uint64_t first_byte, uint6
 
 hipError_t launch_read_stream(const void* d_p, uint64_t n16, unsigned long long* d_sink, int grid, bool nt,
                               hipStream_t s, int variant) {
-    if (variant == 1) {
-        if (nt) {
-            hipLaunchKernelGGL(read_stream_lds_kernel<true>, dim3(grid), dim3(256), 0, s,
-                               reinterpret_cast<gu32x4*>(reinterpret_cast<uintptr_t>(d_p)), n16, d_sink);
-        } else {
-            hipLaunchKernelGGL(read_stream_lds_kernel<false>, dim3(grid), dim3(256), 0, s,
-                               reinterpret_cast<gu32x4*>(reinterpret_cast<uintptr_t>(d_p)), n16, d_sink);
-        }
+    return dsp::pick(hipErrorInvalidValue, [&](auto lds, auto ntc) {
+        const auto kern = lds ? read_stream_lds_kernel<ntc> : read_stream_kernel<ntc>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, reinterpret_cast<gu32x4*>(reinterpret_cast<uintptr_t>(d_p)),
+                           n16, d_sink);
         return hipGetLastError();
-    }
-    if (nt) {
-        hipLaunchKernelGGL(read_stream_kernel<true>, dim3(grid), dim3(256), 0, s,
-                           reinterpret_cast<gu32x4*>(reinterpret_cast<uintptr_t>(d_p)), n16, d_sink);
-    } else {
-        hipLaunchKernelGGL(read_stream_kernel<false>, dim3(grid), dim3(256), 0, s,
-                           reinterpret_cast<gu32x4*>(reinterpret_cast<uintptr_t>(d_p)), n16, d_sink);
-    }
-    return hipGetLastError();
+    }, dsp::Flag{variant == 1}, dsp::Flag{nt});
 }
 
 }  // namespace netcsum

@@ -22,6 +22,7 @@
 #include "netcsum_device.h"
 #include "netcsum_ipparse.h"
 #include "netcsum_kernels.h"
+#include "netcsum_tables.h"
 
 namespace netcsum {
 
@@ -431,54 +432,29 @@ hipError_t launch_pkt_gk(const PktBatchArgs& a, const LaunchCfg& c, hipStream_t 
     } else {
         grid = c.grid > 0 ? c.grid : (int)(((uint64_t)a.n + gpb - 1u) / gpb);
     }
-    if constexpr (!TX && VER == 0) {                             // fragment payload sums (RxBurstSums)
-        if (a.sums_out != nullptr) {
-            if (c.nt) {
-                hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, true, TX, VER, true>), dim3(grid), dim3(256), 0, s, a);
-            } else {
-                hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, false, TX, VER, true>), dim3(grid), dim3(256), 0, s, a);
-            }
-            return hipGetLastError();
-        }
-    }
-    if (!TX && a.sums_out != nullptr) return hipErrorInvalidValue;   // (one IP version: no such instantiation)
-    if (c.nt) {
-        hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, true, TX, VER>), dim3(grid), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, false, TX, VER>), dim3(grid), dim3(256), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <bool VARLEN, bool TX, int VER>
-hipError_t launch_pkt_v(const PktBatchArgs& a, const LaunchCfg& c, hipStream_t s) {
-    switch (c.group_lanes) {
-    case 8:  return c.chunks_per_pass <= 4 ? launch_pkt_gk<8, 4, VARLEN, TX, VER>(a, c, s)
-                                           : launch_pkt_gk<8, 8, VARLEN, TX, VER>(a, c, s);
-    case 16: return c.chunks_per_pass <= 3 ? launch_pkt_gk<16, 3, VARLEN, TX, VER>(a, c, s)
-                                           : launch_pkt_gk<16, 6, VARLEN, TX, VER>(a, c, s);
-    case 32: return c.chunks_per_pass <= 3 ? launch_pkt_gk<32, 3, VARLEN, TX, VER>(a, c, s)
-                                           : launch_pkt_gk<32, 6, VARLEN, TX, VER>(a, c, s);
-    default: return launch_pkt_gk<64, 4, VARLEN, TX, VER>(a, c, s);
-    }
-}
-
-template <int VER>
-hipError_t launch_pkt_ver(const PktBatchArgs& a, const LaunchCfg& c, bool tx, hipStream_t s) {
-    if (a.off) {
-        return tx ? launch_pkt_v<true, true, VER>(a, c, s) : launch_pkt_v<true, false, VER>(a, c, s);
-    }
-    return tx ? launch_pkt_v<false, true, VER>(a, c, s) : launch_pkt_v<false, false, VER>(a, c, s);
+    // fragment payload sums (RxBurstSums): Rx of mixed batches only; one IP version has no such instantiation
+    constexpr bool kSums = !TX && VER == 0;
+    if (!TX && !kSums && a.sums_out != nullptr) return hipErrorInvalidValue;
+    using Sums = std::conditional_t<kSums, dsp::Flag, dsp::Of<false>>;
+    return dsp::pick(hipErrorInvalidValue, [&](auto nt, auto sums) {
+        hipLaunchKernelGGL((pkt_batch_kernel<G, K, VARLEN, nt, TX, VER, sums>), dim3(grid), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }, dsp::Flag{c.nt}, Sums{kSums && a.sums_out != nullptr});
 }
 
 }  // namespace
 
+// ip_ver 4 or 6, else the mixed form; group 8, 16 or 32, else 64; K 4 or 8 chunks per lane at group
+// 8, 3 or 6 at 16 and 32, 4 at 64.
 hipError_t launch_pkt_batch(const PktBatchArgs& a, const LaunchCfg& c, bool tx, int ip_ver, hipStream_t s) {
-    switch (ip_ver) {
-    case 4:  return launch_pkt_ver<4>(a, c, tx, s);
-    case 6:  return launch_pkt_ver<6>(a, c, tx, s);
-    default: return launch_pkt_ver<0>(a, c, tx, s);
-    }
+    const int gl = c.group_lanes;
+    const int g = (gl == 8 || gl == 16 || gl == 32) ? gl : 64;
+    const int k = g == 64 ? 4 : g == 8 ? (c.chunks_per_pass <= 4 ? 4 : 8) : (c.chunks_per_pass <= 3 ? 3 : 6);
+    return dsp::pick_tuple(PktGroupTable{}, hipErrorInvalidValue, [&](auto gc, auto kc) {
+        return dsp::pick(hipErrorInvalidValue, [&](auto varlen, auto txc, auto ver) {
+            return launch_pkt_gk<gc, kc, varlen, txc, ver>(a, c, s);
+        }, dsp::Flag{a.off != nullptr}, dsp::Flag{tx}, dsp::Or<0, 4, 6>{ip_ver});
+    }, g, k);
 }
 
 }  // namespace netcsum

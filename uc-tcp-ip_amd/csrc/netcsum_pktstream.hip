@@ -45,6 +45,7 @@
 #include "netcsum_ipparse.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
+#include "netcsum_tables.h"
 #include "netcsum_v6walk.h"
 
 namespace netcsum {
@@ -1263,14 +1264,11 @@ template <bool WALK>
 hipError_t launch_scatter(const KernelTune& k, const PktBatchArgs& a, const PktTxRecord* rec, hipStream_t s) {
     const int m = tx_flush_mode(k);
     const dim3 g((a.n + 255u) / 256u), b(256);
-    if (m == 1) {
-        hipLaunchKernelGGL((pkt_scatter_kernel<true, false, WALK>), g, b, 0, s, a, rec);
-    } else if (m == 2) {
-        hipLaunchKernelGGL((pkt_scatter_kernel<false, true, WALK>), g, b, 0, s, a, rec);
-    } else {
-        hipLaunchKernelGGL((pkt_scatter_kernel<false, false, WALK>), g, b, 0, s, a, rec);
-    }
-    return hipGetLastError();
+    using Modes = dsp::Table<Tu<true, false>, Tu<false, true>, Tu<false, false>>;      // (WT, WB)
+    return dsp::pick_tuple(Modes{}, hipErrorInvalidValue, [&](auto wt, auto wb) {
+        hipLaunchKernelGGL((pkt_scatter_kernel<wt, wb, WALK>), g, b, 0, s, a, rec);
+        return hipGetLastError();
+    }, m == 1, m == 2);
 }
 
 hipError_t launch_tx_flush(const KernelTune& k, hipStream_t s) {
@@ -1362,15 +1360,13 @@ hipError_t launch_burst_server(const BurstServerArgs& a, int blocks, hipStream_t
     if (blocks < 1 || blocks > kBurstServerMaxBlocks || a.post == nullptr || a.closed == nullptr) {
         return hipErrorInvalidValue;
     }
-    if (sums != nullptr) {
-        BurstServerSumsArgs as{};
+    return dsp::pick(hipErrorInvalidValue, [&](auto sm) {
+        std::conditional_t<sm, BurstServerSumsArgs, BurstServerArgs> as{};
         static_cast<BurstServerArgs&>(as) = a;
-        as.sums = sums;
-        hipLaunchKernelGGL(burst_server_kernel<true>, dim3(blocks), dim3(256), 0, s, as);
-    } else {
-        hipLaunchKernelGGL(burst_server_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    }
-    return hipGetLastError();
+        if constexpr (sm) as.sums = sums;
+        hipLaunchKernelGGL(burst_server_kernel<sm>, dim3(blocks), dim3(256), 0, s, as);
+        return hipGetLastError();
+    }, dsp::Flag{sums != nullptr});
 }
 
 // Strided batches of >= 64-B packets (IPv4, IPv6 or mixed) whose runs span < 2^31 bytes: any gap
@@ -1386,12 +1382,10 @@ bool pkt_stream_supported(const PktBatchArgs& a, int ip_ver, int bound) {
 
 hipError_t launch_pkt_plan(const PktBatchArgs& a, int ip_ver, hipStream_t s) {
     if (a.plan_out == nullptr || a.n == 0u) return hipErrorInvalidValue;
-    const bool vl = a.off != nullptr;
-#define NETCSUM_PP(V_, VL_) \
-    if (ip_ver == V_ && vl == VL_) { hipLaunchKernelGGL((pkt_plan_kernel<V_, VL_>), dim3(1), dim3(256), 0, s, a); return hipGetLastError(); }
-    NETCSUM_PP(4, false) NETCSUM_PP(4, true) NETCSUM_PP(6, false) NETCSUM_PP(6, true) NETCSUM_PP(0, false) NETCSUM_PP(0, true)
-#undef NETCSUM_PP
-    return hipErrorInvalidValue;
+    return dsp::pick(hipErrorInvalidValue, [&](auto ver, auto vl) {
+        hipLaunchKernelGGL((pkt_plan_kernel<ver, vl>), dim3(1), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }, dsp::Of<4, 6, 0>{ip_ver}, dsp::Flag{a.off != nullptr});
 }
 
 hipError_t launch_pkt_stream(const KernelTune& k, const PktBatchArgs& a, int ip_ver, int depth, uint32_t spw, bool nt, bool tx,
@@ -1415,36 +1409,19 @@ hipError_t launch_pkt_stream(const KernelTune& k, const PktBatchArgs& a, int ip_
             return hipErrorInvalidValue;
         }
     }
-    const bool vl = a.off != nullptr;
     // fragment payload sums (a.sums_out): the SUMS instantiations, Rx of mixed batches only
-    if (!tx && a.sums_out != nullptr) {
-        if (ip_ver != 0 || rec != nullptr) return hipErrorInvalidValue;
-#define NETCSUM_PS(D_, B_, VL_)                                                                           \
-    if (depth == D_ && bound == B_ && vl == VL_)                                                          \
-        return nt ? launch_pkt_stream_t<D_, true, false, 0, B_, VL_, true>(k, a, spw, s, nullptr, false)  \
-                  : launch_pkt_stream_t<D_, false, false, 0, B_, VL_, true>(k, a, spw, s, nullptr, false);
-        NETCSUM_PS(4, 0, false) NETCSUM_PS(4, 1, false) NETCSUM_PS(4, 2, false) NETCSUM_PS(4, 3, false)
-        NETCSUM_PS(8, 0, false) NETCSUM_PS(8, 2, false) NETCSUM_PS(8, 3, false)
-        NETCSUM_PS(4, 1, true) NETCSUM_PS(4, 2, true) NETCSUM_PS(8, 2, true)
-#undef NETCSUM_PS
-        return hipErrorInvalidValue;
-    }
-    // every bound with 4 pieces in flight, 8 with bounds 0, 2 and 3; offset/length runs in the
-    // live-piece forms 1 and 2
-#define NETCSUM_P(V_, D_, NT_, TX_, B_, VL_)                                                              \
-    if (ip_ver == V_ && depth == D_ && nt == NT_ && tx == TX_ && bound == B_ && vl == VL_)                 \
-        return launch_pkt_stream_t<D_, NT_, TX_, V_, B_, VL_>(k, a, spw, s, rec, scatter);
-#define NETCSUM_PB(V_, D_, B_, VL_)                                                                       \
-    NETCSUM_P(V_, D_, true, false, B_, VL_) NETCSUM_P(V_, D_, false, false, B_, VL_)                      \
-    NETCSUM_P(V_, D_, true, true, B_, VL_) NETCSUM_P(V_, D_, false, true, B_, VL_)
-#define NETCSUM_PV(V_) NETCSUM_PB(V_, 4, 0, false) NETCSUM_PB(V_, 4, 1, false) NETCSUM_PB(V_, 4, 2, false)     \
-    NETCSUM_PB(V_, 4, 3, false) NETCSUM_PB(V_, 8, 0, false) NETCSUM_PB(V_, 8, 2, false) NETCSUM_PB(V_, 8, 3, false) \
-    NETCSUM_PB(V_, 4, 1, true) NETCSUM_PB(V_, 4, 2, true) NETCSUM_PB(V_, 8, 2, true)
-    NETCSUM_PV(4) NETCSUM_PV(6) NETCSUM_PV(0)
-#undef NETCSUM_PV
-#undef NETCSUM_PB
-#undef NETCSUM_P
-    return hipErrorInvalidValue;
+    const bool sums = !tx && a.sums_out != nullptr;
+    if (sums && (ip_ver != 0 || rec != nullptr)) return hipErrorInvalidValue;
+    return dsp::pick_tuple(PktStreamTable{}, hipErrorInvalidValue, [&](auto d, auto b, auto vl) {
+        if (sums) {
+            return dsp::pick(hipErrorInvalidValue, [&](auto ntc) {
+                return launch_pkt_stream_t<d, ntc, false, 0, b, vl, true>(k, a, spw, s, nullptr, false);
+            }, dsp::Flag{nt});
+        }
+        return dsp::pick(hipErrorInvalidValue, [&](auto ver, auto ntc, auto txc) {
+            return launch_pkt_stream_t<d, ntc, txc, ver, b, vl>(k, a, spw, s, rec, scatter);
+        }, dsp::Of<4, 6, 0>{ip_ver}, dsp::Flag{nt}, dsp::Flag{tx});
+    }, depth, bound, a.off != nullptr);
 }
 
 }  // namespace netcsum

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "netcsum_device.h"
+#include "netcsum_dispatch.h"
 #include "netcsum_kernels.h"
 
 namespace netcsum {
@@ -120,25 +121,8 @@ bool small_supported(const SegBatchArgs& a) {
 // a.tile > 0 (or grid <= 0): one block per contiguous tile of 256 x U x tile segments;
 // a.tile == 0 with grid > 0: grid-stride over that grid.
 hipError_t launch_small_batch(const SegBatchArgs& a, int grid, hipStream_t s) {
-    switch ((a.seg_len + 3u) >> 2) {
-    case 1: return launch_small_nd<1>(a, grid, s);
-    case 2: return launch_small_nd<2>(a, grid, s);
-    case 3: return launch_small_nd<3>(a, grid, s);
-    case 4: return launch_small_nd<4>(a, grid, s);
-    case 5: return launch_small_nd<5>(a, grid, s);
-    case 6: return launch_small_nd<6>(a, grid, s);
-    case 7: return launch_small_nd<7>(a, grid, s);
-    case 8: return launch_small_nd<8>(a, grid, s);
-    case 9: return launch_small_nd<9>(a, grid, s);
-    case 10: return launch_small_nd<10>(a, grid, s);
-    case 11: return launch_small_nd<11>(a, grid, s);
-    case 12: return launch_small_nd<12>(a, grid, s);
-    case 13: return launch_small_nd<13>(a, grid, s);
-    case 14: return launch_small_nd<14>(a, grid, s);
-    case 15: return launch_small_nd<15>(a, grid, s);
-    case 16: return launch_small_nd<16>(a, grid, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dsp::pick(hipErrorInvalidValue, [&](auto nd) { return launch_small_nd<nd>(a, grid, s); },
+                     dsp::Of<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>{(a.seg_len + 3u) >> 2});
 }
 
 }  // namespace netcsum

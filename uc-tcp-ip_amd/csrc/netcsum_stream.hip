@@ -36,6 +36,7 @@
 #include "netcsum_device.h"
 #include "netcsum_kernels.h"
 #include "netcsum_stream.h"
+#include "netcsum_tables.h"
 
 namespace netcsum {
 
@@ -1077,14 +1078,11 @@ hipError_t launch_read_run(const KernelTune& k, const void* d_p, uint64_t n_byte
                            bool sleep) {
     const uint64_t waves = (n_bytes + kProbeRun - 1u) / kProbeRun;
     const uint32_t xcd = stream_xcd_mode(k, 0);
-    if (sleep) {
-        hipLaunchKernelGGL(read_run_kernel<2>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(k, 5), s,
+    return dsp::pick(hipErrorInvalidValue, [&](auto sl) {
+        hipLaunchKernelGGL(read_run_kernel<sl>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(k, 5), s,
                            static_cast<const uint8_t*>(d_p), n_bytes, d_sink, xcd);
-    } else {
-        hipLaunchKernelGGL(read_run_kernel<0>, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), stream_lds_bytes(k, 5), s,
-                           static_cast<const uint8_t*>(d_p), n_bytes, d_sink, xcd);
-    }
-    return hipGetLastError();
+        return hipGetLastError();
+    }, dsp::Or<0, 2>{sleep ? 2 : 0});
 }
 
 // Packed segments of >= 1 KiB (stride == len): the form the library picks by default (C2, C5).
@@ -1094,18 +1092,11 @@ bool stream_dense(const SegBatchArgs& a) {
 
 namespace {
 
-template <int D>
-hipError_t launch_stream_d(const KernelTune& k, const SegBatchArgs& a, uint32_t spw, bool nt, hipStream_t s) {
-    const int ph = stream_ph(a);
-    const bool one = stream_one(a);
-#define NETCSUM_L(PH_, NT_, ONE_) \
-    if (ph == PH_ && nt == NT_ && one == ONE_) return launch_stream_t<D, PH_, NT_, ONE_>(k, a, spw, s);
-#define NETCSUM_L2(PH_) NETCSUM_L(PH_, true, true) NETCSUM_L(PH_, true, false) NETCSUM_L(PH_, false, true) \
-    NETCSUM_L(PH_, false, false)
-    NETCSUM_L2(0) NETCSUM_L2(1) NETCSUM_L2(2)
-#undef NETCSUM_L2
-#undef NETCSUM_L
-    return hipErrorInvalidValue;
+// seg_stream_kernel's instantiations: f(D, PH, NT, ONE) for the batch, for the launch and the
+// occupancy query alike; miss for a depth other than 4, 6 or 8.
+template <typename R, typename F>
+R with_stream_kernel(int depth, const SegBatchArgs& a, bool nt, R miss, F&& f) {
+    return dsp::pick(miss, f, StreamDepth{depth}, dsp::Of<0, 1, 2>{stream_ph(a)}, dsp::Flag{nt}, dsp::Flag{stream_one(a)});
 }
 
 }  // namespace
@@ -1134,42 +1125,23 @@ uint32_t stream_spw(const SegBatchArgs& a, uint64_t waves) {
 }
 
 int stream_occupancy(int depth, const SegBatchArgs& a, bool nt) {
-    int occ = 0;
-    hipError_t e = hipErrorInvalidValue;
-    const int ph = stream_ph(a);
-    const bool one = stream_one(a);
-#define NETCSUM_OCC(D_, PH_, NT_, ONE_)                                                                   \
-    if (depth == D_ && ph == PH_ && nt == NT_ && one == ONE_) {                                           \
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, seg_stream_kernel<D_, PH_, NT_, ONE_>, 256, 0); \
-    }
-#define NETCSUM_OCC2(D_, PH_) NETCSUM_OCC(D_, PH_, true, true) NETCSUM_OCC(D_, PH_, true, false) \
-    NETCSUM_OCC(D_, PH_, false, true) NETCSUM_OCC(D_, PH_, false, false)
-#define NETCSUM_OCC3(D_) NETCSUM_OCC2(D_, 0) NETCSUM_OCC2(D_, 1) NETCSUM_OCC2(D_, 2)
-    NETCSUM_OCC3(4) NETCSUM_OCC3(6) NETCSUM_OCC3(8)
-#undef NETCSUM_OCC3
-#undef NETCSUM_OCC2
-#undef NETCSUM_OCC
-    return (e == hipSuccess && occ > 0) ? occ : 1;
+    return with_stream_kernel(depth, a, nt, 1, [](auto d, auto ph, auto ntc, auto one) {
+        int occ = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, seg_stream_kernel<d, ph, ntc, one>, 256, 0);
+        return (e == hipSuccess && occ > 0) ? occ : 1;
+    });
 }
 
 hipError_t launch_stream_batch(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, bool nt, hipStream_t s) {
     if (spw == 0u || spw > kMaxRun) return hipErrorInvalidValue;
     if (a.seg_off != nullptr) {                       // varlen: depth 4 or 8
-        const int ph = stream_ph(a);
-#define NETCSUM_V(D_, PH_, NT_) \
-        if ((depth == 8) == (D_ == 8) && ph == PH_ && nt == NT_) return launch_stream_varlen_t<D_, PH_, NT_>(k, a, spw, s);
-        NETCSUM_V(4, 0, true) NETCSUM_V(4, 0, false) NETCSUM_V(4, 1, true) NETCSUM_V(4, 1, false)
-        NETCSUM_V(4, 2, true) NETCSUM_V(4, 2, false) NETCSUM_V(8, 0, true) NETCSUM_V(8, 0, false)
-        NETCSUM_V(8, 1, true) NETCSUM_V(8, 1, false) NETCSUM_V(8, 2, true) NETCSUM_V(8, 2, false)
-#undef NETCSUM_V
-        return hipErrorInvalidValue;
+        return dsp::pick(hipErrorInvalidValue, [&](auto d, auto ph, auto ntc) {
+            return launch_stream_varlen_t<d, ph, ntc>(k, a, spw, s);
+        }, VarlenDepth{depth}, dsp::Of<0, 1, 2>{stream_ph(a)}, dsp::Flag{nt});
     }
-    switch (depth) {
-    case 4: return launch_stream_d<4>(k, a, spw, nt, s);
-    case 6: return launch_stream_d<6>(k, a, spw, nt, s);
-    case 8: return launch_stream_d<8>(k, a, spw, nt, s);
-    default: return hipErrorInvalidValue;
-    }
+    return with_stream_kernel(depth, a, nt, hipErrorInvalidValue, [&](auto d, auto ph, auto ntc, auto one) {
+        return launch_stream_t<d, ph, ntc, one>(k, a, spw, s);
+    });
 }
 
 hipError_t launch_live_varlen(const KernelTune& k, const SegBatchArgs& a, int depth, uint32_t spw, hipStream_t s) {
@@ -1177,14 +1149,9 @@ hipError_t launch_live_varlen(const KernelTune& k, const SegBatchArgs& a, int de
     // PH 2 loads 5 aligned 16-B chunks of each pseudo-header: <= 64 B from any start (stream_supported's
     // limit, checked here too so that no caller can reach the kernel with a longer one)
     if (a.pseudo != nullptr && a.pseudo_len > 64u) return hipErrorInvalidValue;
-    const int ph = stream_ph(a);
-    const bool cmp = live_compact(k);
-#define NETCSUM_LV(D_, PH_) \
-    if (depth == D_ && ph == PH_) return cmp ? launch_live_varlen_t<D_, PH_, true, true>(k, a, spw, s) \
-                                             : launch_live_varlen_t<D_, PH_, true, false>(k, a, spw, s);
-    NETCSUM_LV(4, 0) NETCSUM_LV(4, 1) NETCSUM_LV(4, 2) NETCSUM_LV(8, 0) NETCSUM_LV(8, 1) NETCSUM_LV(8, 2)
-#undef NETCSUM_LV
-    return hipErrorInvalidValue;
+    return dsp::pick(hipErrorInvalidValue, [&](auto d, auto ph, auto cmp) {
+        return launch_live_varlen_t<d, ph, true, cmp>(k, a, spw, s);
+    }, LiveDepth{depth}, dsp::Of<0, 1, 2>{stream_ph(a)}, dsp::Flag{live_compact(k)});
 }
 
 hipError_t launch_chain_live_records(const KernelTune& k, const ChainBatchArgs& c, uint32_t* rec, uint32_t cap, int depth,
@@ -1199,15 +1166,10 @@ hipError_t launch_chain_live_records(const KernelTune& k, const ChainBatchArgs& 
     a.out = rec;
     a.xcd = stream_xcd_mode(k, 1);
     const dim3 grid((unsigned)((((uint64_t)cap + spw - 1u) / spw + 3u) / 4u));
-#define NETCSUM_LC(D_)                                                                                         \
-    if (depth == D_) {                                                                                         \
-        if (cmp) hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, true, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw); \
-        else hipLaunchKernelGGL((seg_live_varlen_kernel<D_, 0, true, false, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw); \
-        return hipGetLastError();                                                                              \
-    }
-    NETCSUM_LC(4) NETCSUM_LC(8)
-#undef NETCSUM_LC
-    return hipErrorInvalidValue;
+    return dsp::pick(hipErrorInvalidValue, [&](auto d, auto cmpc) {
+        hipLaunchKernelGGL((seg_live_varlen_kernel<d, 0, true, cmpc, true>), grid, dim3(256), stream_lds_bytes(k, 0), s, a, spw);
+        return hipGetLastError();
+    }, LiveDepth{depth}, dsp::Flag{cmp});
 }
 
 }  // namespace netcsum
